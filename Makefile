@@ -12,7 +12,7 @@ ifeq ($(TUNE),1)
 export CME_TUNE = 1
 endif
 
-.PHONY: all build test test-asan test-gpu bench smoke occupancy clean
+.PHONY: all build test test-asan test-gpu bench bench-full smoke occupancy clean
 
 all: build
 
@@ -33,6 +33,10 @@ test-gpu: build
 
 bench: build
 	$(PY) bench.py
+
+# the headline plus every other figure and check of the benchmark
+bench-full: build
+	$(PY) bench.py --full
 
 smoke: build
 	$(PY) -c "import __graft_entry__ as g; g.smoke()"

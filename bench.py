@@ -7,6 +7,16 @@ launched under torch.distributed.run (one rank per GPU). W untimed steps, then
 EXACTLY K timed steps bracketed by barrier + synchronize, max over ranks; rank
 0 prints one JSON line.
 
+A plain run does only what the headline figure needs: set-up, spin-up, the W
+warmup and K timed steps of the headline field, the JSON line. ``--full`` adds
+every other measurement and check to the same line: the bitwise self-test of
+the timed path, the finiteness check, the uniform-IC figure next to the
+random-init headline, the distributed schedule at N = 1, the other arithmetic,
+and BASELINE configs #1-#4 (CPU transpose, transpose / scan / SpMV).
+``--dump-outputs DIR`` writes the field the headline run ended with (the
+owned interior after its last timed step, or a fixed seeded sample of it) as
+``DIR/state_rank<r>.npy`` so that two builds can be compared value for value.
+
 A "step" is one full timestep of the global grid: the FTCS sweep of every
 point plus the halo exchange between neighbouring ranks (1-D stripes, async
 mode: deep interior overlapped with the exchange, borders after it). With
@@ -307,6 +317,35 @@ def auto_tblock(points_per_rank: int, kernel: str = "pipe") -> int:
     return 4 if points_per_rank <= 16384 * 16384 // 8 else 3
 
 
+DUMP_BYTES = 32 << 20  # per run, over all ranks (fp32 values)
+DUMP_SEED = 20120401
+
+
+def dump_outputs(directory: str, sim, rank: int, world: int) -> None:
+    """``--dump-outputs``: this rank's owned interior of the current state (what
+    a caller of ``sim.run`` reads back) as ``state_rank<r>.npy``, float32. A
+    subdomain above this rank's share of DUMP_BYTES is sampled instead: the
+    values at a fixed set of points (drawn without the device's generator, from
+    DUMP_SEED, the rank and the subdomain's origin and shape), in draw order."""
+    import numpy as np
+    import torch
+
+    sim.finish()
+    os.makedirs(directory, exist_ok=True)
+    parts = []
+    cap = max(1, DUMP_BYTES // 4 // max(1, world) // max(1, len(sim.subs)))
+    for s in sim.subs.values():
+        g, H = s.grid, s.grid.H
+        own = g.buf[g.cur, H:H + g.ny, H:H + g.nx]
+        if g.ny * g.nx > cap:
+            rng = np.random.default_rng([DUMP_SEED, rank, s.blk.x0, s.blk.y0, g.nx, g.ny])
+            flat = torch.from_numpy(rng.integers(0, g.ny * g.nx, size=cap, dtype=np.int64)).to(own.device)
+            own = own[flat // g.nx, flat % g.nx]
+        parts.append(own.to(torch.float32).cpu().numpy())
+    out = parts[0] if len(parts) == 1 else np.concatenate([a.reshape(-1) for a in parts])
+    np.save(os.path.join(directory, f"state_rank{rank}.npy"), out)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -351,10 +390,18 @@ def main() -> int:
     ap.add_argument("--ic", choices=["uniform", "random", "both"], default="both",
                     help="both (default): time K steps from the reference's uniform IC 5.0 (value_uniform) and from "
                          "a random-init field (the headline value); uniform: the uniform IC only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the timed path's bitwise self-test and "
+                         "finiteness check, the uniform-IC figure next to a random-init headline, and at N = 1 the "
+                         "distributed schedule, the other arithmetic and BASELINE configs #1-#4")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline's timed steps, write the state they ended with as "
+                         "DIR/state_rank<r>.npy (float32; a fixed seeded sample of a subdomain above 32 MB)")
     ap.add_argument("--no-primitives", dest="primitives", action="store_false",
-                    help="N = 1: skip the BASELINE configs #2-#4 (transpose / scan / SpMV) measured after the stencil")
+                    help="--full, N = 1: skip the BASELINE configs #2-#4 (transpose / scan / SpMV) measured after "
+                         "the stencil")
     ap.add_argument("--no-arith-compare", dest="arith_compare", action="store_false",
-                    help="N = 1: skip timing the other arithmetic (fma <-> fast) on the same fields")
+                    help="--full, N = 1: skip timing the other arithmetic (fma <-> fast) on the same fields")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal only: every rank on cuda:0 with a gloo control plane and the IPC transport "
                          "(exercises the multi-rank flow on a 1-GPU box; the number is not a scaling result)")
@@ -422,8 +469,9 @@ def main() -> int:
         sim.run(k)
 
     # the timed path's bitwise self-test at N = 1 (N > 1: enable_native above)
+    # (--full only: it sets up and runs two more solvers)
     selftest_ok = info["selftest"] if use_native else None
-    if on_gpu and comm.size == 1:
+    if on_gpu and comm.size == 1 and args.full:
         selftest_ok = selftest(comm, dev, args)
 
     def barrier_sync():
@@ -491,8 +539,16 @@ def main() -> int:
         comm.allreduce_(bad, "max")
         return bool(bad.item() == 0)
 
-    secs = timed(args.steps)
-    sanity_ok = sane()
+    # the headline field: random-init unless --ic uniform (or the CPU dry
+    # run); the uniform figure next to a random-init headline is --full's
+    headline_random = on_gpu and args.ic in ("both", "random")
+    secs = sanity_ok = None
+    if args.full or not headline_random:
+        secs = timed(args.steps)
+        if not headline_random and args.dump_outputs:
+            dump_outputs(args.dump_outputs, sim, rank, comm.size)
+        if args.full:
+            sanity_ok = sane()
 
     # N = 1: the distributed native schedule (cme_heat_dist_run, the loop the
     # N > 1 points run, exchange off) on the same grid and the same uniform
@@ -501,7 +557,7 @@ def main() -> int:
     # with 5 warmup steps right after the host-side gap the first passes ran
     # at a lower clock, 0.166 vs 0.1315 ms/step in bench_dist_rank.py)
     secs_dist1 = None
-    if on_gpu and comm.size == 1 and args.kernel == "pipe":
+    if args.full and on_gpu and comm.size == 1 and args.kernel == "pipe":
         run_d = lambda k: sim.run_native(k, transport=2)  # noqa: E731
         spin_up(run_d)
         for s in sim.subs.values():
@@ -519,7 +575,7 @@ def main() -> int:
     # ms/step, steady state 0.16-0.17; profiles/heat_random_ic_r4.md), then
     # the field is reset to the random init and timed.
     secs_random = None
-    if on_gpu and args.ic in ("both", "random"):
+    if headline_random:
         gen = torch.Generator(device=dev)
         gen.manual_seed(1234 + rank)
         rand_init = {}
@@ -533,7 +589,10 @@ def main() -> int:
         sim.exchange(sim._cur()).wait()
         sync()
         secs_random = timed(args.steps)
-        sanity_ok = sanity_ok and sane()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, sim, rank, comm.size)
+        if args.full:
+            sanity_ok = sanity_ok and sane()
 
     # N = 1: the other arithmetic on the same two fields with the same
     # protocol, in the same record: the reassociated pass next to
@@ -542,7 +601,8 @@ def main() -> int:
     # to an explicitly chosen fast headline
     secs_cmp = {}
     cmp_arith = {"fma": "fast", "fast": "fma"}.get(args.arith)
-    if on_gpu and comm.size == 1 and cmp_arith and args.arith_compare and args.order == 8 and args.kernel == "pipe":
+    if (args.full and on_gpu and comm.size == 1 and cmp_arith and args.arith_compare and args.order == 8
+            and args.kernel == "pipe"):
         sim_f = DistHeat(p, comm, torch.float32, dev, variant=args.variant, tblock=args.tblock,
                          fma={"fma": True, "fast": "fast"}[cmp_arith], kernel=args.kernel)
         run_f = sim_f.run
@@ -561,13 +621,13 @@ def main() -> int:
         torch.cuda.empty_cache()
 
     prims = {}
-    if comm.size == 1 and args.primitives:
+    if args.full and comm.size == 1 and args.primitives:
         # config #1 (CPU / OpenMP, no GPU involved)
         try:
             prims.update(bench_cpu_transpose())
         except Exception as e:  # noqa: BLE001 - recorded in the JSON
             prims["cpu_transpose_error"] = f"{type(e).__name__}: {e}"[:300]
-    if on_gpu and comm.size == 1 and args.primitives:
+    if args.full and on_gpu and comm.size == 1 and args.primitives:
         # configs #2-#4 are extra keys: a failure there is recorded, and the
         # stencil line still prints
         try:
@@ -589,7 +649,6 @@ def main() -> int:
     # random-init inputs"); the reference's uniform IC is
     # value_uniform / ms_per_step_uniform
     secs_uniform = secs
-    headline_random = secs_random is not None
     if headline_random:
         secs = secs_random
     eff = pts * bpp * args.steps / secs / 1e9
@@ -643,12 +702,13 @@ def main() -> int:
             "pct_peak_hbm_per_gpu": round(100.0 * hbm / args.gpus / 8000.0, 1),
             "gpoints_per_s": round(pts * args.steps / secs / 1e9, 2),
             # a failed bitwise self-test of the timed path invalidates the record
-            "sanity_ok": bool(sanity_ok and selftest_ok is not False),
+            # (both are --full's: null in a plain run)
+            "sanity_ok": None if sanity_ok is None else bool(sanity_ok and selftest_ok is not False),
             "selftest": selftest_ok,
             "native_selftest": (info["selftest"] if comm.size > 1 and on_gpu else None),
             "spinup_steps": spin,
         }
-        if headline_random:
+        if headline_random and secs_uniform is not None:
             rec["ms_per_step_uniform"] = round(secs_uniform * 1e3 / args.steps, 4)
             rec["value_uniform"] = round(pts * bpp * args.steps / secs_uniform / 1e9, 2)
             rec["data_uniform"] = "the reference's uniform IC 5.0, Dirichlet BCs 0/10/0/10"
