@@ -17,6 +17,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from ..ops.sort import sort
 from ..ops.text import (digraph_histogram, letter_histogram, match_counts, residue_histograms, sanitize,
                         vigenere)
 
@@ -76,8 +77,11 @@ def solve_cipher(cipher: bytes | np.ndarray, device=None, out_path: str | None =
     if verbose:
         for i in range(26):
             print(f"{chr(97 + i)} {hist[i] / n:g}")
-    dg = digraph_histogram(t).cpu().numpy().ravel()
-    order = np.argsort(-dg, kind="stable")[:20]
+    dg_t = digraph_histogram(t).reshape(-1)
+    # the reference's sort_by_key(counts, digraph ids, greater<int>()): stable, so ties keep the lower id first
+    ids = torch.arange(dg_t.numel(), dtype=torch.int32, device=dg_t.device)
+    order = sort(dg_t, ids, descending=True)[1][:20].cpu().numpy()
+    dg = dg_t.cpu().numpy()
     npairs = n // 2
     if verbose:
         for i in order:

@@ -66,6 +66,18 @@ class BlockedGraph:
         return self.inv_deg.numel()
 
 
+def _edge_order(key: torch.Tensor) -> torch.Tensor:
+    """Stable sorting permutation of the int64 (block, row) keys: the edges of
+    one (block, row) keep their CSR order. Still ``torch.sort``:
+    ``ops.sort.argsort`` gives the same permutation and measured faster on
+    this shape (2^21 nodes: 2.30 against 2.72 ms for the whole preprocessing,
+    ``benchmarks/bench_sort.py --block-columns``), but one row of the 64-bit
+    sort's table (int64 keys with int64 values at 48M) does not beat
+    ``torch.sort`` yet, and until every row does this caller stays where it
+    was (profiles/sort64_r7.md)."""
+    return torch.sort(key, stable=True).indices
+
+
 def block_columns(g: CSRGraph, blocks: int = 4) -> BlockedGraph:
     """Column-blocked copy of ``g`` (one-time preprocessing with tensor ops,
     on g's device): a sweep then gathers from one 1/blocks slice of the vector
@@ -77,7 +89,7 @@ def block_columns(g: CSRGraph, blocks: int = 4) -> BlockedGraph:
     bs = (n + blocks - 1) // blocks
     blk = g.edges.to(torch.int64) // bs
     key = blk * n + row
-    order = torch.sort(key, stable=True).indices
+    order = _edge_order(key)
     edges = g.edges[order].contiguous()
     counts = torch.bincount(key, minlength=blocks * n)
     rp = torch.zeros(blocks * n + 1, dtype=torch.int64, device=dev)

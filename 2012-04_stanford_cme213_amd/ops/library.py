@@ -15,7 +15,8 @@ Ops (schema in each docstring; "!" = mutated in place):
 ``heat_stepn``            nsteps (2-4) timesteps in one HBM pass (temporal blocking)
 ``scan``                  inclusive / exclusive prefix sum
 ``segmented_scan``        inclusive segmented sum scan (uint8 heads or int32 bitmask)
-``sort`` / ``sort_by_key`` stable LSD radix sort (keys, or keys + 32-bit values)
+``sort`` / ``sort_by_key`` stable LSD radix sort, 32- and 64-bit keys (+ 4- / 8-byte values)
+``argsort``               int64 stable sorting permutation (ascending or descending)
 ``spmv_csr``              y = A x, A in CSR (rp, col, val)
 ``transpose``             2-D fp32 transpose
 ``sgemm`` / ``gemv``      C = A B (MFMA), y = A x
@@ -103,7 +104,7 @@ def _(x, flags):
 # ------------------------------------------------------------------ sort
 @torch.library.custom_op(f"{NS}::sort", mutates_args=())
 def sort(keys: Tensor) -> Tensor:
-    """sort(Tensor keys) -> Tensor   (stable radix sort; int32 / uint32 / float32)"""
+    """sort(Tensor keys) -> Tensor   (stable radix sort; int32 / uint32 / float32 / int64 / uint64 / float64)"""
     return _fresh(_sort.sort(keys), keys)
 
 
@@ -114,7 +115,8 @@ def _(keys):
 
 @torch.library.custom_op(f"{NS}::sort_by_key", mutates_args=())
 def sort_by_key(keys: Tensor, values: Tensor) -> tuple[Tensor, Tensor]:
-    """sort_by_key(Tensor keys, Tensor values) -> (Tensor, Tensor)"""
+    """sort_by_key(Tensor keys, Tensor values) -> (Tensor, Tensor)
+    (4-byte values with 32-bit keys, 4- or 8-byte values with 64-bit keys)"""
     k, v = _sort.sort(keys, values)
     return _fresh(k, keys, values), _fresh(v, keys, values)
 
@@ -123,6 +125,17 @@ def sort_by_key(keys: Tensor, values: Tensor) -> tuple[Tensor, Tensor]:
 def _(keys, values):
     return (torch.empty_like(keys, memory_format=torch.contiguous_format),
             torch.empty_like(values, memory_format=torch.contiguous_format))
+
+
+@torch.library.custom_op(f"{NS}::argsort", mutates_args=())
+def argsort(keys: Tensor, descending: bool = False) -> Tensor:
+    """argsort(Tensor keys, bool descending=False) -> Tensor   (int64 stable sorting permutation)"""
+    return _sort.argsort(keys, descending)
+
+
+@argsort.register_fake
+def _(keys, descending=False):
+    return torch.empty(keys.shape, dtype=torch.int64, device=keys.device)
 
 
 # ------------------------------------------------------------------ sparse / dense linear algebra
@@ -186,6 +199,6 @@ def _(x, flags):
 
 OPS = {
     "heat_step": heat_step, "heat_stepn": heat_stepn, "scan": scan, "segmented_scan": segmented_scan,
-    "sort": sort, "sort_by_key": sort_by_key, "spmv_csr": spmv_csr, "transpose": transpose, "sgemm": sgemm,
+    "sort": sort, "sort_by_key": sort_by_key, "argsort": argsort, "spmv_csr": spmv_csr, "transpose": transpose, "sgemm": sgemm,
     "gemv": gemv, "copy_if": copy_if,
 }

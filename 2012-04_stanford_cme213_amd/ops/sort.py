@@ -3,7 +3,13 @@ merge-path merge sort, and the hw4 OpenMP radix / merge sorts.
 
 Keys: uint32 natively; int32 and float32 are mapped to order-preserving
 uint32 codes (sign-bit flip / IEEE total-order trick) and back -- inside the
-onesweep kernels (first pass loads, last pass stores), elsewhere by tensor ops.
+GPU kernels (first pass loads, last pass stores), on the CPU by tensor ops.
+64-bit keys (uint64 / int64 / float64, with 4- or 8-byte values) take the
+same route through 64-bit codes: ``csrc/hip/radix64.hip`` on the GPU
+(reduce-then-scan only), ``cme_cpu_radix_sort_kv_u64`` on the CPU.
+Descending order complements the code, so equal keys keep their input order
+(``torch.sort(stable=True, descending=True)``); :func:`argsort` is a
+key-value sort of 32-bit positions, widened to int64 at the end.
 
 GPU radix algorithms: "radix" = reduce-then-scan (``csrc/hip/sort.hip``:
 upsweep + one-launch count scan + downsweep per 8-bit digit), "onesweep"
@@ -29,6 +35,12 @@ _ext.proto(_ext.CPU_PROTOS, "cme_cpu_radix_sort_u32", "ppqii")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_radix_sort_serial_u32", "ppqi")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_merge_sort_i32", "ppqqqp")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_radix_sort_kv_u32", "ppppqii")
+_ext.proto(_ext.HIP_PROTOS, "cme_radix_sort64", "ppppppqiiiipp")
+_ext.proto(_ext.HIP_PROTOS, "cme_radix_sort64_tile", "")
+_ext.proto(_ext.CPU_PROTOS, "cme_cpu_radix_sort_kv_u64", "ppppqiii")
+
+_MIN32 = -(2 ** 31)
+_MIN64 = -(2 ** 63)
 
 
 def _to_u32(k: torch.Tensor) -> torch.Tensor:
@@ -55,12 +67,55 @@ def _from_u32(u: torch.Tensor, dtype) -> torch.Tensor:
     return (i ^ mask).view(torch.float32)
 
 
+def _to_code64(k: torch.Tensor, descending: bool, plain: bool = False) -> torch.Tensor:
+    """Order codes of 64-bit keys as a fresh int64 tensor holding the
+    unsigned code's bits: uint64 as is, int64 with the sign bit flipped,
+    float64 in IEEE total order; complemented for descending order.
+    ``plain``: non-negative integer keys taken as they are (key_bits < 64)."""
+    i = k.view(torch.int64)
+    if plain or k.dtype == torch.uint64:
+        c = i.clone()
+    elif k.dtype == torch.int64:
+        c = i ^ _MIN64
+    else:
+        c = i ^ torch.where(i < 0, -1, _MIN64)
+    return ~c if descending else c
+
+
+def _from_code64(c: torch.Tensor, dtype, descending: bool, plain: bool = False) -> torch.Tensor:
+    if descending:
+        c = ~c
+    if plain or dtype == torch.uint64:
+        return c.view(dtype)
+    if dtype == torch.int64:
+        return c ^ _MIN64
+    return (c ^ torch.where(c >= 0, -1, _MIN64)).view(torch.float64)
+
+
+def _reverse32(k: torch.Tensor) -> torch.Tensor:
+    """32-bit keys whose ascending order is the descending order of ``k``
+    (an involution; equal keys stay equal, so a stable sort keeps their input
+    order): the complement for integers, the sign-bit flip for float32 --
+    in the IEEE total order that is the exact reverse, NaNs included."""
+    i = k.view(torch.int32)
+    return (i ^ _MIN32 if k.dtype == torch.float32 else ~i).view(k.dtype)
+
+
 _ws: dict = {}
 _os_ws: dict = {}
 _os_epochs: dict = {}
 _OS_TILE = 8192
 _OS_EPOCH_LIMIT = 1 << 27  # radix.hip: granule tag = epoch * 4 + pass, 30 bits
 _MODES = {torch.uint32: 0, torch.int32: 1, torch.float32: 2}
+_MODES64 = {torch.uint64: 0, torch.int64: 1, torch.float64: 2}  # cme_radix_sort64: | 4 = descending
+RADIX64_TILE = 8192  # keys per downsweep tile of the 64-bit sort (= cme_radix_sort64_tile())
+
+
+def _check_32bit_algo(dtype, algo: str) -> None:
+    if dtype in _MODES64:
+        raise TypeError(f"algo={algo!r} sorts 32-bit keys only; {dtype} keys: algo='radix'")
+    if dtype not in _MODES:
+        raise TypeError(f"unsupported key dtype {dtype}")
 
 
 def _onesweep_ws(keys: torch.Tensor) -> tuple[torch.Tensor, int]:
@@ -107,8 +162,7 @@ def _merge(keys: torch.Tensor, values: torch.Tensor | None):
     Keys-only and key-value tiles are block-sorted by an LDS radix sort
     (tuning knob merge_block_sort). A 4-way pass schedule lives in the tuning
     library (cme_merge_sort4_tune; measured slower: profiles/sort_r6.md)."""
-    if keys.dtype not in _MODES:
-        raise TypeError(f"unsupported key dtype {keys.dtype}")
+    _check_32bit_algo(keys.dtype, "merge")
     k = keys.contiguous()
     out, tmp = torch.empty_like(k), torch.empty_like(k)
     vp = vo = vt = None
@@ -151,13 +205,70 @@ def _rts(keys: torch.Tensor, values: torch.Tensor | None, key_bits: int):
     return (out, vout) if values is not None else out
 
 
+def _check_values64(values: torch.Tensor, n: int) -> None:
+    if values.element_size() not in (4, 8) or values.numel() != n or values.dim() != 1:
+        raise TypeError("values: one 4- or 8-byte value per 64-bit key")
+
+
+def _rts64(keys: torch.Tensor, values: torch.Tensor | None, key_bits: int, descending: bool):
+    """Reduce-then-scan LSD radix sort of 64-bit keys (cme_radix_sort64):
+    eight passes at full width, only those covering ``key_bits`` below it;
+    the key kind and the descending complement are fused into the first
+    pass's loads and the last pass's stores, the input is untouched, values
+    (4 or 8 bytes each) move as raw bits."""
+    n = keys.numel()
+    dtype = keys.dtype
+    if key_bits < 64 and dtype == torch.float64:
+        raise TypeError("key_bits < 64 needs non-negative integer keys")
+    mode = (0 if key_bits < 64 else _MODES64[dtype]) | (4 if descending else 0)
+    bits = 64 if key_bits >= 64 else max(1, int(key_bits))
+    k = keys.contiguous()
+    out, tmp = torch.empty_like(k), torch.empty_like(k)
+    vp = vo = vt = None
+    vb = 0
+    if values is not None:
+        _check_values64(values, n)
+        v = values.contiguous()
+        vb = v.element_size()
+        vout, vtmp = torch.empty_like(v), torch.empty_like(v)
+        vp, vo, vt = v.data_ptr(), vout.data_ptr(), vtmp.data_ptr()
+    tiles = (n + 4095) // 4096
+    ws = _workspace(keys.device, min(tiles, 4096) * 256 * 4 + 256 * 4 + 256)  # = cme_radix_ws_bytes
+    _ext.call_hip("cme_radix_sort64", k.data_ptr(), out.data_ptr(), tmp.data_ptr(), vp, vo, vt, n, mode, vb, 0, bits,
+                  ws.data_ptr(), _ext.stream_ptr(keys.device))
+    return (out, vout) if values is not None else out
+
+
+def _cpu_sort64(keys: torch.Tensor, values: torch.Tensor | None, num_bits: int, key_bits: int, descending: bool):
+    """OpenMP LSD radix sort of 64-bit keys (cme_cpu_radix_sort_kv_u64) over
+    order codes made by tensor ops."""
+    n = keys.numel()
+    dtype = keys.dtype
+    plain = key_bits < 64
+    if plain and dtype == torch.float64:
+        raise TypeError("key_bits < 64 needs non-negative integer keys")
+    k = _to_code64(keys.contiguous(), descending, plain)
+    kt = torch.empty_like(k)
+    vp = vt = None
+    vb = 0
+    if values is not None:
+        _check_values64(values, n)
+        v = values.contiguous().clone()
+        vtmp = torch.empty_like(v)
+        vb = v.element_size()
+        vp, vt = v.data_ptr(), vtmp.data_ptr()
+    _ext.call_cpu("cme_cpu_radix_sort_kv_u64", k.data_ptr(), kt.data_ptr(), vp, vt, n, vb, num_bits,
+                  min(64, max(1, int(key_bits))))
+    out = _from_code64(k, dtype, descending, plain)
+    return (out, v) if values is not None else out
+
+
 def _onesweep(keys: torch.Tensor, values: torch.Tensor | None, key_bits: int):
     from .scan import _check_lookback
 
     n = keys.numel()
     dtype = keys.dtype
-    if dtype not in _MODES:
-        raise TypeError(f"unsupported key dtype {dtype}")
+    _check_32bit_algo(dtype, "onesweep")
     if key_bits < 32 and dtype not in (torch.int32, torch.uint32):
         raise TypeError("key_bits < 32 needs non-negative integer keys")
     mode = 0 if key_bits < 32 else _MODES[dtype]
@@ -198,18 +309,46 @@ def _workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
 
 
 def sort(keys: torch.Tensor, values: torch.Tensor | None = None, algo: str = "radix", num_bits: int = 8,
-         key_bits: int = 32):
-    """Sort a 1-D tensor (optionally carrying int32/uint32/float32 values).
+         key_bits: int | None = None, descending: bool = False):
+    """Sort a 1-D tensor of int32 / uint32 / float32 or int64 / uint64 /
+    float64 keys, optionally carrying one value per key: 4-byte values with
+    32-bit keys, 4- or 8-byte values of any dtype (moved as raw bits) with
+    64-bit keys. Stable; floats in IEEE total order (-NaN, -inf, ..., -0, +0,
+    ..., +inf, +NaN); ``descending`` is the exact reverse with equal keys
+    still in input order (``torch.sort(stable=True, descending=True)``).
     GPU algos: "radix" (reduce-then-scan, stable; "radix_rts" is an alias),
-    "onesweep" (decoupled look-back, stable), "merge" (stable). CPU algos: "radix" (OpenMP,
-    ``num_bits`` per pass), "radix_serial", "merge" (OpenMP tasks, keys only).
-    ``key_bits`` < 32 (GPU radix, non-negative integer keys below
-    ``2**key_bits``) runs only the passes covering those bits -- a counting
-    sort when ``key_bits <= 8``. Returns sorted keys (and values)."""
+    "onesweep" (decoupled look-back, stable), "merge" (stable); 64-bit keys:
+    "radix" only. CPU algos: "radix" (OpenMP, ``num_bits`` per pass),
+    "radix_serial", "merge" (OpenMP tasks, keys only), the last two for
+    32-bit keys. ``key_bits`` (None = the key width) below the key width
+    (radix, non-negative integer keys below ``2**key_bits``) runs only the
+    passes covering those bits -- a counting sort when ``key_bits <= 8``.
+    Returns sorted keys (and values)."""
     if keys.dim() != 1:
         raise ValueError("1-D keys expected")
     n = keys.numel()
+    if n >= 1 << 32:
+        raise ValueError("sort: fewer than 2**32 keys")
     dtype = keys.dtype
+    if dtype in _MODES64:
+        if algo not in ("radix", "radix_rts"):
+            raise TypeError(f"algo={algo!r} sorts 32-bit keys only; {dtype} keys: algo='radix'")
+        kb = 64 if key_bits is None else int(key_bits)
+        if values is not None:
+            _check_values64(values, n)
+        if not keys.is_cuda and n > 0:
+            return _cpu_sort64(keys, values, num_bits, kb, descending)
+        if n <= 1:
+            return (keys.clone(), values.clone()) if values is not None else keys.clone()
+        return _rts64(keys, values, kb, descending)
+    if descending:
+        # 32-bit keys: the ascending sort of the order-reversed keys (equal
+        # keys stay equal, so stability carries over), mapped back
+        if dtype not in _MODES:
+            raise TypeError(f"unsupported key dtype {dtype}")
+        res = sort(_reverse32(keys), values, algo, num_bits, key_bits)
+        return (_reverse32(res[0]), res[1]) if values is not None else _reverse32(res)
+    key_bits = 32 if key_bits is None else int(key_bits)
     if keys.is_cuda and algo in ("radix", "radix_rts", "onesweep"):
         if n <= 1:
             return (keys.clone(), values.clone()) if values is not None else keys.clone()
@@ -251,6 +390,27 @@ def sort(keys: torch.Tensor, values: torch.Tensor | None = None, algo: str = "ra
     else:
         raise ValueError(algo)
     return _from_u32(k, dtype)
+
+
+def argsort(keys: torch.Tensor, descending: bool = False) -> torch.Tensor:
+    """The stable sorting permutation of 1-D ``keys`` (any dtype :func:`sort`
+    takes, GPU or CPU) as int64: ``keys[argsort(keys)]`` is ``sort(keys)``,
+    and equal keys keep their input order, as ``torch.sort(keys, stable=True,
+    descending=...).indices``. A key-value radix sort carrying 32-bit
+    positions (the sort's limit is n < 2**32), widened once at the end."""
+    if keys.dim() != 1:
+        raise ValueError("1-D keys expected")
+    n = keys.numel()
+    if n >= 1 << 32:
+        raise ValueError("sort: fewer than 2**32 keys")
+    if keys.dtype not in _MODES and keys.dtype not in _MODES64:
+        raise TypeError(f"unsupported key dtype {keys.dtype}")
+    if n < 1 << 31:
+        pos = torch.arange(n, dtype=torch.int32, device=keys.device)
+    else:  # positions from 2**31 wrap into the sign bit and are unwrapped below
+        pos = torch.arange(n, dtype=torch.int64, device=keys.device).to(torch.int32)
+    order = sort(keys, pos, descending=descending)[1].to(torch.int64)
+    return order if n < 1 << 31 else order & 0xFFFFFFFF
 
 
 def merge_sort_cpu(keys: torch.Tensor, sort_threshold: int, merge_threshold: int) -> tuple[torch.Tensor, int]:

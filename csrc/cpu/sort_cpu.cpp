@@ -61,6 +61,62 @@ void radix_pass(const uint32_t* in, uint32_t* out, long long n, int shift, int b
     }
 }
 
+// The same pass over 64-bit order codes; V = the value type (4- or 8-byte raw
+// bits), vin == nullptr for keys only
+template <typename V>
+void radix_pass64(const uint64_t* in, uint64_t* out, long long n, int shift, int bits, int nblocks, const V* vin,
+                  V* vout) {
+    const uint32_t nb = 1u << bits;
+    const uint64_t mask = nb - 1;
+    std::vector<uint64_t> hist((size_t)nblocks * nb, 0);
+    const long long bs = (n + nblocks - 1) / nblocks;
+#pragma omp parallel for schedule(static)
+    for (int b = 0; b < nblocks; ++b) {
+        uint64_t* h = &hist[(size_t)b * nb];
+        const long long e = std::min(n, (b + 1) * bs);
+        for (long long i = b * bs; i < e; ++i) ++h[(in[i] >> shift) & mask];
+    }
+    // hist[b][d] -> offset of block b's first key of digit d
+    uint64_t run = 0;
+    for (uint32_t d = 0; d < nb; ++d) {
+        for (int b = 0; b < nblocks; ++b) {
+            const uint64_t c = hist[(size_t)b * nb + d];
+            hist[(size_t)b * nb + d] = run;
+            run += c;
+        }
+    }
+#pragma omp parallel for schedule(static)
+    for (int b = 0; b < nblocks; ++b) {
+        uint64_t* o = &hist[(size_t)b * nb];
+        const long long e = std::min(n, (b + 1) * bs);
+        if (vin) {
+            for (long long i = b * bs; i < e; ++i) {
+                const uint64_t d = o[(in[i] >> shift) & mask]++;
+                out[d] = in[i];
+                vout[d] = vin[i];
+            }
+        } else {
+            for (long long i = b * bs; i < e; ++i) out[o[(in[i] >> shift) & mask]++] = in[i];
+        }
+    }
+}
+
+template <typename V>
+void radix_sort64(uint64_t* keys, uint64_t* ktmp, V* vals, V* vtmp, long long n, int num_bits, int key_bits) {
+    const int nblocks = std::max(1, omp_get_max_threads() * 4);
+    uint64_t *in = keys, *out = ktmp;
+    V *vi = vals, *vo = vtmp;
+    for (int shift = 0; shift < key_bits; shift += num_bits) {
+        radix_pass64<V>(in, out, n, shift, std::min(num_bits, key_bits - shift), nblocks, vi, vo);
+        std::swap(in, out);
+        std::swap(vi, vo);
+    }
+    if (in != keys) {
+        std::memcpy(keys, in, n * sizeof(uint64_t));
+        if (vals) std::memcpy(vals, vi, n * sizeof(V));
+    }
+}
+
 void merge_serial(const int* a, long long na, const int* b, long long nb, int* out) {
     std::merge(a, a + na, b, b + nb, out);
 }
@@ -139,6 +195,24 @@ CME_CPU_EXPORT int cme_cpu_radix_sort_kv_u32(uint32_t* keys, uint32_t* ktmp, uin
         std::memcpy(keys, in, n * sizeof(uint32_t));
         std::memcpy(vals, vi, n * sizeof(uint32_t));
     }
+    return 0;
+}
+
+// The same over 64-bit order codes (the caller maps int64 / float64 keys and
+// descending order to codes): values optional, val_bytes 0 (none: vals and
+// vtmp unused), 4 or 8, moved as raw bits. Sorted keys and values end in
+// `keys` / `vals`.
+CME_CPU_EXPORT int cme_cpu_radix_sort_kv_u64(uint64_t* keys, uint64_t* ktmp, void* vals, void* vtmp, long long n,
+                                             int val_bytes, int num_bits, int key_bits) {
+    if (num_bits < 1 || num_bits > 16 || key_bits < 1 || key_bits > 64) return 1;
+    if (val_bytes != 0 && val_bytes != 4 && val_bytes != 8) return 1;
+    if (val_bytes != 0 && (!vals || !vtmp)) return 1;
+    if (val_bytes == 8)
+        radix_sort64<uint64_t>(keys, ktmp, (uint64_t*)vals, (uint64_t*)vtmp, n, num_bits, key_bits);
+    else if (val_bytes == 4)
+        radix_sort64<uint32_t>(keys, ktmp, (uint32_t*)vals, (uint32_t*)vtmp, n, num_bits, key_bits);
+    else
+        radix_sort64<uint32_t>(keys, ktmp, nullptr, nullptr, n, num_bits, key_bits);
     return 0;
 }
 
