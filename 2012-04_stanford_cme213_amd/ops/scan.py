@@ -5,6 +5,9 @@
   (``slides/Lecture16.pdf``; ``my-refs/scan.pdf`` Fig. 5).
 * :func:`reduce` -- sum / max / min; the lecture's shared-memory tree
   (``slides/Lecture05.pdf`` 15-16) as ``algo="tree"``.
+* Both take float32 / int32 and int64 / float64 (``scan`` also uint32); the
+  64-bit kernels are ``csrc/hip/scan64.hip`` (``algo="rts"`` / ``"lookback"``
+  only; everything else here is 32-bit).
 * :func:`segmented_scan` -- inclusive, head-flag segmented scan (Lecture21;
   nvr-2008-003), optionally fused with an element-wise multiply: the final
   project's ``a *= x[k]; b = segscan(a)`` step (``hw/hw_final/programming/
@@ -29,10 +32,19 @@ _ext.proto(_ext.CPU_PROTOS, "cme_cpu_scan", "ppqii")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_reduce", "pqiip")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_segscan", "ppppiq")
 
+# native dtype codes; 3 / 4 are the 64-bit kernels (csrc/hip/scan64.hip), the
+# codes algorithms.py uses for int64 / float64 as well
 _DT = {torch.float32: 0, torch.int32: 1}
 _DT_SCAN = {torch.float32: 0, torch.int32: 1, torch.uint32: 2}
+_DT64 = {torch.int64: 3, torch.float64: 4}
 _OPS = {"sum": 0, "max": 1, "min": 2}
 TILE = 4096
+TILE64 = 8192  # elements per tile of the 64-bit look-back scan (scan64.h kScan64Tile; "rts" tiles are half)
+_ALGOS64 = ("rts", "lookback")
+# "auto" for int64: the look-back measured faster than reduce-then-scan at
+# both 2^25 and 2^27 elements (benchmarks/bench_primitives.py --only scan64,
+# profiles/scan64_r8.md)
+_AUTO_INT64 = "lookback"
 
 _ws_cache: dict = {}
 
@@ -72,6 +84,48 @@ def _lookback_ws(x: torch.Tensor) -> tuple[torch.Tensor, int]:
         # later epochs (>= 1) ignore; the count is NOT restarted: before a
         # replay, words of the earlier epochs are still there
         return t, 0
+    e = _epochs[k] + 1
+    if e >= _EPOCH_LIMIT:
+        t.zero_()
+        e = 1
+    _epochs[k] = e
+    return t, e
+
+
+_ext.proto(_ext.HIP_PROTOS, "cme_scan64_info", "qp")
+
+
+def scan64_launch_info(n: int, device: torch.device | str = "cuda") -> dict:
+    """How the 64-bit scans of ``n`` elements are launched on ``device``:
+    ``tile`` (elements), ``tiles``, ``lookback_workgroups`` (the persistent,
+    co-resident grid of ``algo="lookback"``), ``rts_chunks`` and
+    ``rts_tiles_per_chunk`` (``algo="rts"``, whose tiles are ``rts_tile``
+    elements), ``lookback_ws_bytes``."""
+    import ctypes
+
+    info = (ctypes.c_longlong * 7)()
+    with torch.cuda.device(torch.device(device)):
+        _ext.call_hip("cme_scan64_info", n, ctypes.addressof(info))
+    keys = ("tile", "tiles", "lookback_workgroups", "rts_chunks", "rts_tiles_per_chunk", "lookback_ws_bytes", "rts_tile")
+    return dict(zip(keys, (int(v) for v in info)))
+
+
+def _lookback64_ws(x: torch.Tensor) -> tuple[torch.Tensor, int]:
+    """Descriptor array and epoch of a 64-bit look-back launch. As
+    :func:`_lookback_ws`, but an array and an epoch count of their own per
+    (device, stream): a slot is two 8-byte granules there (twice the bytes),
+    and a 32-bit and a 64-bit scan issued back to back on one stream never
+    read each other's words."""
+    tiles = (x.numel() + TILE64 - 1) // TILE64
+    nbytes = 32 * tiles + 32 * (tiles // 64 + 1) + 64  # scan64.hip lb64_ws_bytes
+    k = (f"lookback64:{_ext.stream_ptr(x.device)}", x.device.index)
+    t = _ws_cache.get(k)
+    if t is None or t.numel() < nbytes:
+        t = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=x.device)
+        _ws_cache[k] = t
+        _epochs[k] = 0
+    if torch.cuda.is_current_stream_capturing():
+        return t, 0  # the graph zeroes the array at every replay (see _lookback_ws)
     e = _epochs[k] + 1
     if e >= _EPOCH_LIMIT:
         t.zero_()
@@ -143,21 +197,50 @@ def _check_lookback(x: torch.Tensor, before: bool = False) -> None:
 
 def scan(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = None,
          algo: str = "auto") -> torch.Tensor:
-    """Prefix sum of a 1-D contiguous float32/int32/uint32 tensor.
-    algo: "auto" ("lookback" for integers, whose sums are exact in any order;
-    "rts" for float32, whose fixed summation tree is bitwise reproducible --
-    look-back's float prefixes depend on which predecessor had published its
-    inclusive value), "lookback" (single pass), "rts" (reduce-then-scan with DPP wave
-    scans, deterministic), "blelloch" / "hillis" (reduce-then-scan whose block
-    level is the lecture's LDS tree algorithm), "blelloch_mlevel" /
-    "hillis_mlevel" (the recursive scan-then-add of my-refs/scan.pdf Fig. 5)."""
+    """Prefix sum of a 1-D contiguous float32/int32/uint32/int64/float64 tensor.
+    algo: "auto" ("lookback" for 32-bit integers, whose sums are exact in any
+    order; "rts" for float32 and float64, whose fixed summation tree is bitwise
+    reproducible -- look-back's float prefixes depend on which predecessor had
+    published its inclusive value, so neither float32 nor float64 is bitwise
+    reproducible with it; int64: see ``_AUTO_INT64``), "lookback" (single
+    pass), "rts" (reduce-then-scan with DPP wave scans, deterministic),
+    "blelloch" / "hillis" (reduce-then-scan whose block level is the lecture's
+    LDS tree algorithm), "blelloch_mlevel" / "hillis_mlevel" (the recursive
+    scan-then-add of my-refs/scan.pdf Fig. 5).
+
+    int64 and float64 take "rts" and "lookback" only (a ``TypeError`` names
+    them otherwise). int64 sums wrap modulo 2^64, as ``torch.cumsum`` and numpy
+    do; a uint64 sum is the int64 sum of the same bits (``.view``). The data
+    need only be 8-byte aligned (``x[1:]`` is fine). ``out`` (same dtype and
+    length, contiguous) may be ``x`` itself for "rts" and "lookback"."""
     if not x.is_contiguous():
         x = x.contiguous()
+    if out is not None and (out.dtype != x.dtype or out.numel() != x.numel() or out.device != x.device
+                            or not out.is_contiguous()):
+        raise ValueError("scan: out must be a contiguous tensor of x's dtype, length and device")
     out = torch.empty_like(x) if out is None else out
     n = x.numel()
+    wide = x.dtype in _DT64
+    if wide and algo not in ("auto",) + _ALGOS64:
+        raise TypeError(f"scan: algo {algo!r} is 32-bit only; {x.dtype} input takes "
+                        + " or ".join(repr(a) for a in _ALGOS64))
     if algo == "auto":
-        algo = "rts" if x.dtype == torch.float32 else "lookback"
-    if x.is_cuda:
+        if wide:
+            algo = "rts" if x.dtype == torch.float64 else _AUTO_INT64
+        else:
+            algo = "rts" if x.dtype == torch.float32 else "lookback"
+    if x.is_cuda and wide:
+        s = _ext.stream_ptr(x.device)
+        if algo == "lookback":
+            _check_lookback(x, before=True)
+            ws, epoch = _lookback64_ws(x)
+            _ext.call_hip("cme_scan", x.data_ptr(), out.data_ptr(), n, _DT64[x.dtype], int(exclusive),
+                          ws.data_ptr(), epoch, s)
+            _check_lookback(x)
+        else:
+            _ext.call_hip("cme_scan_rts", x.data_ptr(), out.data_ptr(), n, _DT64[x.dtype], int(exclusive),
+                          workspace(x.device, 8192, "rts").data_ptr(), s)
+    elif x.is_cuda:
         s = _ext.stream_ptr(x.device)
         if algo == "lookback":
             _check_lookback(x, before=True)
@@ -186,20 +269,28 @@ def scan(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = No
         else:
             raise ValueError(f"unknown scan algo {algo!r}")
     else:
-        _ext.call_cpu("cme_cpu_scan", x.data_ptr(), out.data_ptr(), n, _DT_SCAN[x.dtype], int(exclusive))
+        _ext.call_cpu("cme_cpu_scan", x.data_ptr(), out.data_ptr(), n, _DT64[x.dtype] if wide else _DT_SCAN[x.dtype],
+                      int(exclusive))
     return out
 
 
 def reduce(x: torch.Tensor, op: str = "sum", algo: str = "vector") -> torch.Tensor:
-    """Full reduction of a float32/int32 tensor; returns a 0-d tensor on x's device."""
+    """Full reduction (``op``: "sum", "max", "min") of a float32/int32/int64/
+    float64 tensor; returns a 0-d tensor on x's device. An int64 sum wraps
+    modulo 2^64. ``algo="tree"`` (the lecture's LDS tree, sum only) is 32-bit
+    only and raises a ``TypeError`` for 64-bit input."""
     x = x.contiguous()
+    wide = x.dtype in _DT64
+    if wide and algo != "vector":
+        raise TypeError(f"reduce: algo {algo!r} is 32-bit only; {x.dtype} input takes 'vector'")
+    dt = _DT64[x.dtype] if wide else _DT[x.dtype]
     out = torch.empty((), dtype=x.dtype, device=x.device)
     if x.is_cuda:
         part = workspace(x.device, 2048 * 4, "reduce")
-        _ext.call_hip("cme_reduce", x.data_ptr(), x.numel(), _DT[x.dtype], _OPS[op], 0 if algo == "vector" else 1,
+        _ext.call_hip("cme_reduce", x.data_ptr(), x.numel(), dt, _OPS[op], 0 if algo == "vector" else 1,
                       part.data_ptr(), out.data_ptr(), _ext.stream_ptr(x.device))
     else:
-        _ext.call_cpu("cme_cpu_reduce", x.data_ptr(), x.numel(), _DT[x.dtype], _OPS[op], out.data_ptr())
+        _ext.call_cpu("cme_cpu_reduce", x.data_ptr(), x.numel(), dt, _OPS[op], out.data_ptr())
     return out
 
 

@@ -5,6 +5,8 @@ per measurement with the reference number it is compared against.
   copy       1 GiB 16-B copy (achievable-HBM calibration)
   scan       2^26 elements: look-back / Blelloch / Hillis-Steele (BASELINE #11)
   reduce     2^26 elements
+  scan64     int64 / float64 scans and sums at 2^25 and 2^27 against the copy
+             rate of the same run (profiles/scan64_r8.md)
   spmvscan   the 15 final-project shapes (BASELINE #19-21, synthetic values)
   cipher     19.76 MB moby-dick x16 (BASELINE #1-3)
   pagerank   2^21 nodes, avg 8 edges, 20 iterations (BASELINE #5)
@@ -102,6 +104,58 @@ def main():
         ms = timeit(lambda: x.sum())
         emit(bench="reduce", algo="torch.sum", n=n, ms=ms, GBps=4 * n / ms / 1e6)
         del x, y, xi, yi
+
+    if want("scan64"):
+        # int64 / float64 at 2^25 and 2^27: the arms of one (dtype, size)
+        # alternate call by call in this process (in an order reshuffled every
+        # round), every call of an arm takes the next of three operand sets
+        # (cache-defeated: 3 x 16 B x n is far past the 256 MB Infinity Cache at
+        # both sizes) and the copy of the same operands is one of the arms, so
+        # every share is against the copy rate of the same run.
+        def alternate(arms, rounds=12, warm=2):
+            import random
+
+            order = list(arms)
+            rnd = random.Random(0)
+            ts = {a: [] for a in arms}
+            turn = {a: 0 for a in arms}
+            for r in range(rounds + warm):
+                rnd.shuffle(order)  # no arm always runs behind the same predecessor
+                for name in order:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    arms[name](turn[name] % 3)
+                    e1.record()
+                    e1.synchronize()
+                    turn[name] += 1
+                    if r >= warm:
+                        ts[name].append(e0.elapsed_time(e1))
+            return {a: (sorted(t)[len(t) // 2], min(t), max(t)) for a, t in ts.items()}
+
+        for dt in (torch.int64, torch.float64):
+            for n in (1 << 25, 1 << 27):
+                if dt == torch.int64:
+                    xs = [torch.randint(-2 ** 40, 2 ** 40, (n,), device=dev, dtype=dt) for _ in range(3)]
+                else:
+                    xs = [torch.rand(n, device=dev, dtype=dt) for _ in range(3)]
+                ys = [torch.empty_like(x) for x in xs]
+                arms = {
+                    "copy": lambda k: ys[k].copy_(xs[k]),
+                    "rts": lambda k: sc.scan(xs[k], True, ys[k], "rts"),
+                    "lookback": lambda k: sc.scan(xs[k], True, ys[k], "lookback"),
+                    "torch.cumsum": lambda k: torch.cumsum(xs[k], 0, out=ys[k]),
+                    "reduce": lambda k: sc.reduce(xs[k], "sum"),
+                    "torch.sum": lambda k: xs[k].sum(),
+                }
+                res = alternate(arms)
+                copy_bps = 16 * n / res["copy"][0] / 1e6
+                for name, (ms, lo, hi) in res.items():
+                    per = 8 if name in ("reduce", "torch.sum") else 16  # bytes per element of the model
+                    emit(bench="scan64", dtype=str(dt).split(".")[1], n=n, arm=name, ms=round(ms, 4),
+                         ms_min=round(lo, 4), ms_max=round(hi, 4), model_B_per_elem=per,
+                         GBps=round(per * n / ms / 1e6, 1), share_of_copy=round(per * n / ms / 1e6 / copy_bps, 3))
+                sc.check_lookback(dev)
+                del xs, ys, arms
 
     if want("spmvscan"):
         from cme213x.models.spmv_scan import BENCH_SHAPES, REF_MS, SpmvScanSolver, generate

@@ -106,7 +106,8 @@ def bench64(a, knobs) -> int:
 def bench_block_columns(a) -> int:
     """Preprocessing time of graph.block_columns on the hw1 PageRank graph
     (2^21 nodes, 8 edges per node) with this library's argsort and with the
-    torch.sort(stable=True) it replaced, same process, same graph."""
+    torch.sort(stable=True) it replaced, same process, same graph; then with
+    the row-pointer scan as torch.cumsum and as this library's int64 scan."""
     import torch
 
     from cme213x.ops import graph as G
@@ -125,6 +126,30 @@ def bench_block_columns(a) -> int:
         print(json.dumps({"bench": "block_columns", "nodes": 1 << 21, "edges": g.edges.numel(), "blocks": blocks,
                           "ms_argsort64": round(res["argsort64"], 4), "ms_torch_sort": round(res["torch_stable"], 4)}),
               flush=True)
+    # the row-pointer scan: the torch.cumsum it was against this library's int64
+    # scan (shipped), the two forms alternated in this process, five timings of each
+    # form (the spread of repeated runs of one form is what a difference
+    # between the forms has to exceed)
+    from cme213x.ops.scan import scan
+
+    forms = (("torch_cumsum", lambda c, out: torch.cumsum(c, 0, out=out)),
+             ("scan64", lambda c, out: scan(c, out=out)))
+    shipped_rp = G._row_pointers
+    runs = {name: [] for name, _ in forms}
+    for _ in range(5):
+        for name, f in forms:
+            G._row_pointers = f
+            try:
+                runs[name].append(_time(lambda: G.block_columns(g, 4), a.reps))
+            finally:
+                G._row_pointers = shipped_rp
+    rec = {"bench": "block_columns_row_pointers", "nodes": 1 << 21, "edges": g.edges.numel(), "blocks": 4}
+    for name, ts in runs.items():
+        ts = sorted(ts)
+        rec[f"ms_{name}"] = round(ts[len(ts) // 2], 4)
+        rec[f"ms_{name}_min"] = round(ts[0], 4)
+        rec[f"ms_{name}_max"] = round(ts[-1], 4)
+    print(json.dumps(rec), flush=True)
     return 0
 
 

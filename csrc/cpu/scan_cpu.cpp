@@ -42,7 +42,14 @@ void scan_impl(const T* in, T* out, long long n, bool exclusive) {
 template <typename T>
 void reduce_impl(const T* in, long long n, int op, T* out) {
     T acc;
-    if (op == 0) {
+    if (op == 0 && sizeof(T) == 8) {
+        // 64-bit elements accumulate in their own type: uint64 sums wrap
+        // modulo 2^64 (int64 is summed through it), double has no wider oracle
+        T a = T(0);
+#pragma omp parallel for reduction(+ : a)
+        for (long long i = 0; i < n; ++i) a += in[i];
+        acc = a;
+    } else if (op == 0) {
         double a = 0;  // fp64 accumulation for the oracle
 #pragma omp parallel for reduction(+ : a)
         for (long long i = 0; i < n; ++i) a += (double)in[i];
@@ -65,6 +72,9 @@ CME_CPU_EXPORT int cme_cpu_scan(const void* in, void* out, long long n, int dtyp
     if (dtype == 0) scan_impl((const float*)in, (float*)out, n, exclusive);
     else if (dtype == 1) scan_impl((const int*)in, (int*)out, n, exclusive);
     else if (dtype == 2) scan_impl((const uint32_t*)in, (uint32_t*)out, n, exclusive);
+    // int64 in unsigned arithmetic: the sum wraps modulo 2^64 (signed overflow is undefined)
+    else if (dtype == 3) scan_impl((const uint64_t*)in, (uint64_t*)out, n, exclusive);
+    else if (dtype == 4) scan_impl((const double*)in, (double*)out, n, exclusive);
     else return 1;
     return 0;
 }
@@ -73,6 +83,9 @@ CME_CPU_EXPORT int cme_cpu_reduce(const void* in, long long n, int dtype, int op
     if (n <= 0) return 1;
     if (dtype == 0) reduce_impl((const float*)in, n, op, (float*)out);
     else if (dtype == 1) reduce_impl((const int*)in, n, op, (int*)out);
+    else if (dtype == 3 && op == 0) reduce_impl((const uint64_t*)in, n, op, (uint64_t*)out);
+    else if (dtype == 3) reduce_impl((const int64_t*)in, n, op, (int64_t*)out);
+    else if (dtype == 4) reduce_impl((const double*)in, n, op, (double*)out);
     else return 1;
     return 0;
 }

@@ -11,10 +11,13 @@
 //  * cme_reduce         two-pass block reduction (grid-stride 16-B loads, DPP
 //                       wave reduce, LDS across waves) and the lecture's
 //                       shared-memory tree (`s = blockDim/2; s >>= 1`) variant.
+//                       dtype codes 3 / 4 (int64 / float64) of cme_scan, cme_scan_rts
+//                       and cme_reduce go to scan64.hip.
 //  * cme_segscan        single-pass segmented inclusive scan with head flags.
 //  * cme_spmv_scan_step fused final-project step: a[i] *= xx[i] then inclusive
 //                       segmented scan of a (segment heads as a bitmask).
 #include "scan_kernels.h"
+#include "scan64.h"
 
 // The look-back give-up word: pinned, mapped host memory (lookback.h). One per
 // process; device stores reach it directly, the host reads it without a sync.
@@ -43,13 +46,16 @@ CME_EXPORT int cme_lookback_timeout_word(void** host_word) {
 }
 
 
-// Reduce-then-scan (deterministic). ws: >= 4 * 1024 bytes.
+// Reduce-then-scan (deterministic). dtype: 0 f32, 1 i32, 2 u32, 3 i64, 4 f64
+// (scan64.hip). ws: >= 8 * 1024 bytes.
 CME_EXPORT int cme_scan_rts(const void* in, void* out, long long n, int dtype, int exclusive, void* ws, void* stream) {
     hipStream_t s = as_stream(stream);
     switch (dtype) {
         case 0: return launch_rts<float>((const float*)in, (float*)out, n, exclusive, ws, s);
         case 1: return launch_rts<int>((const int*)in, (int*)out, n, exclusive, ws, s);
         case 2: return launch_rts<uint32_t>((const uint32_t*)in, (uint32_t*)out, n, exclusive, ws, s);
+        case 3:
+        case 4: return scan64_rts(in, out, n, dtype, exclusive, ws, s);
         default: return (int)hipErrorInvalidValue;
     }
 }
@@ -68,7 +74,8 @@ CME_EXPORT int cme_scan_tree(const void* in, void* out, long long n, int dtype, 
     }
 }
 
-// dtype: 0 f32, 1 i32, 2 u32. ws: >= 8*ceil(n/4096) + 16 bytes.
+// dtype: 0 f32, 1 i32, 2 u32: ws >= 8*ceil(n/4096) + 16 bytes; 3 i64, 4 f64
+// (scan64.hip): ws >= cme_scan64_info's byte count, an array of its own.
 // epoch: see launch_scan (0 = zero the workspace here)
 CME_EXPORT int cme_scan(const void* in, void* out, long long n, int dtype, int exclusive, void* ws, unsigned epoch,
                         void* stream) {
@@ -77,6 +84,8 @@ CME_EXPORT int cme_scan(const void* in, void* out, long long n, int dtype, int e
         case 0: return launch_scan<float>((const float*)in, (float*)out, n, exclusive, ws, s, epoch);
         case 1: return launch_scan<int>((const int*)in, (int*)out, n, exclusive, ws, s, epoch);
         case 2: return launch_scan<uint32_t>((const uint32_t*)in, (uint32_t*)out, n, exclusive, ws, s, epoch);
+        case 3:
+        case 4: return scan64_lookback(in, out, n, dtype, exclusive, ws, s, epoch);
         default: return (int)hipErrorInvalidValue;
     }
 }
@@ -112,12 +121,14 @@ CME_EXPORT int cme_scan_mlevel(const void* in, void* out, long long n, int dtype
     CME_LAUNCH_STATUS();
 }
 
-// op: 0 sum, 1 max, 2 min; dtype 0 f32, 1 i32. algo 0 = DPP/vector, 1 = LDS tree (sum only).
-// part: >= 2048 elements of scratch. result written to `out` (device).
+// op: 0 sum, 1 max, 2 min; dtype 0 f32, 1 i32, 3 i64, 4 f64 (scan64.hip; algo
+// 0 only). algo 0 = DPP/vector, 1 = LDS tree (sum only, 32-bit only).
+// part: >= 8192 bytes of scratch. result written to `out` (device).
 CME_EXPORT int cme_reduce(const void* in, long long n, int dtype, int op, int algo, void* part, void* out,
                           void* stream) {
     hipStream_t s = as_stream(stream);
     const int grid = 1024;
+    if (dtype == 3 || dtype == 4) return algo == 0 ? reduce64(in, n, dtype, op, part, out, s) : (int)hipErrorInvalidValue;
 #define RED(T, OP)                                                                                              \
     hipLaunchKernelGGL((reduce_partial_kernel<T, OP>), dim3(grid), dim3(256), 0, s, (const T*)in, n, (T*)part, OP()); \
     hipLaunchKernelGGL((reduce_final_kernel<T, OP>), dim3(1), dim3(1024), 0, s, (const T*)part, grid, (T*)out, OP());

@@ -101,6 +101,7 @@ template <> __device__ __forceinline__ float OpMax::identity<float>() { return -
 template <> __device__ __forceinline__ double OpMax::identity<double>() { return -__builtin_huge_val(); }
 template <> __device__ __forceinline__ int OpMax::identity<int>() { return (int)0x80000000; }
 template <> __device__ __forceinline__ uint32_t OpMax::identity<uint32_t>() { return 0u; }
+template <> __device__ __forceinline__ long long OpMax::identity<long long>() { return (long long)(1ull << 63); }
 struct OpMin {
     template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a < b ? a : b; }
     template <typename T> __device__ __forceinline__ static T identity();
@@ -109,6 +110,7 @@ template <> __device__ __forceinline__ float OpMin::identity<float>() { return _
 template <> __device__ __forceinline__ double OpMin::identity<double>() { return __builtin_huge_val(); }
 template <> __device__ __forceinline__ int OpMin::identity<int>() { return 0x7fffffff; }
 template <> __device__ __forceinline__ uint32_t OpMin::identity<uint32_t>() { return 0xffffffffu; }
+template <> __device__ __forceinline__ long long OpMin::identity<long long>() { return 0x7fffffffffffffffll; }
 
 // Inclusive scan across the 64 lanes of a wave (all lanes must be active).
 template <typename Op = OpAdd, typename T>
