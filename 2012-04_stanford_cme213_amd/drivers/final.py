@@ -1,7 +1,7 @@
 """Final-project drivers.
 
-    python -m cme213x fp a.txt x.txt [check] [--algo lookback|wave|serial] [--graph]  -> b.txt (+ b_cpu.txt)
-    python -m cme213x checker a.txt x.txt b.txt    (reference_spMVscan-released)
+    python -m cme213x fp a.txt x.txt [check] [--algo lookback|wave|serial] [--graph] [--double]  -> b.txt (+ b_cpu.txt)
+    python -m cme213x checker a.txt x.txt b.txt [--double]   (reference_spMVscan-released)
     python -m cme213x readmm <matrix.mtx> <outdir> [q N]   (readMM.py)
     python -m cme213x genfp <name|n p> <outdir> [--q Q] [--iters N]
 """
@@ -23,29 +23,34 @@ def fp_main(argv=None) -> int:
         algo = argv[i + 1]
         del argv[i:i + 2]
     graph = "--graph" in argv
-    argv = [a for a in argv if a != "--graph"]
+    double = "--double" in argv  # float64 state and arithmetic; b.txt with 17 significant digits
+    argv = [a for a in argv if a not in ("--graph", "--double")]
     if len(argv) < 2:
         print('Run command: ./fp "file a.txt" "file x.txt"')
         return 0
-    res = run_fp(argv[0], argv[1], cpu_check=len(argv) >= 3, algo=algo, graph=graph)
+    res = run_fp(argv[0], argv[1], cpu_check=len(argv) >= 3, algo=algo, graph=graph, double=double)
     if "relL2" in res:
         print(f"relative L2 error {res['relL2']:g}, relative Linf error {res['relLinf']:g}")
     return 0
 
 
 def checker_main(argv=None) -> int:
-    """``checker a.txt x.txt b.txt [--legacy]``: the instructor checker
-    (reference_spMVscan-released.cu); ``--legacy`` uses the older O(len^2)
-    serial algorithm of aux/CheckOutput/serialMV.cu (small inputs)."""
+    """``checker a.txt x.txt b.txt [--legacy] [--double]``: the instructor
+    checker (reference_spMVscan-released.cu); ``--legacy`` uses the older
+    O(len^2) serial algorithm of aux/CheckOutput/serialMV.cu (small inputs).
+    ``--double`` reads a.txt and x.txt as float64 instead of rounding them to
+    float32 first, as ``fp --double`` does: the reference then starts from the
+    numbers a double run started from."""
     from ..models.spmv_scan import errors, load, reference_solution, reference_solution_quadratic
 
     argv = list(sys.argv[1:] if argv is None else argv)
     legacy = "--legacy" in argv
-    argv = [a for a in argv if a != "--legacy"]
+    double = "--double" in argv
+    argv = [a for a in argv if a not in ("--legacy", "--double")]
     if len(argv) != 3:
-        print("usage: checker a.txt x.txt b.txt [--legacy]")
+        print("usage: checker a.txt x.txt b.txt [--legacy] [--double]")
         return 1
-    prob = load(argv[0], argv[1])
+    prob = load(argv[0], argv[1], dtype=np.float64 if double else np.float32)
     b = np.fromfile(argv[2], sep=" ")
     ref = reference_solution_quadratic(prob) if legacy else reference_solution(prob)
     e = errors(ref, b[:prob.n])

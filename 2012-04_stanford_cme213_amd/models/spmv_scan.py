@@ -33,10 +33,10 @@ from ..utils.timer import EventTimer
 
 @dataclass
 class SpmvScanProblem:
-    a: np.ndarray  # float32 [n]
+    a: np.ndarray  # float32 [n] (float64 when loaded / generated in double)
     s: np.ndarray  # int32 [p]   (s[0] = 0, s[p-1] = n)
     k: np.ndarray  # int32 [n]   (0 <= k < q)
-    x: np.ndarray  # float32 [q]
+    x: np.ndarray  # float32 [q] (float64 in double)
     iters: int
 
     @property
@@ -58,13 +58,15 @@ class SpmvScanProblem:
         assert self.k.min() >= 0 and self.k.max() < self.q, "k out of range"
 
 
-def load(a_path: str, x_path: str) -> SpmvScanProblem:
+def load(a_path: str, x_path: str, dtype=np.float32) -> SpmvScanProblem:
+    """``dtype``: the element type of ``a`` and ``x`` (float32, or float64 to
+    keep every digit of the files)."""
     tok = np.fromfile(a_path, sep=" ")
     n, p, q, N = (int(v) for v in tok[:4])
-    a = tok[4:4 + n].astype(np.float32)
+    a = tok[4:4 + n].astype(dtype)
     s = tok[4 + n:4 + n + p].astype(np.int64).astype(np.int32)
     k = tok[4 + n + p:4 + n + p + n].astype(np.int64).astype(np.int32)
-    x = np.fromfile(x_path, sep=" ")[:q].astype(np.float32)
+    x = np.fromfile(x_path, sep=" ")[:q].astype(dtype)
     prob = SpmvScanProblem(a, s, k, x, N)
     prob.validate()
     return prob
@@ -80,20 +82,22 @@ def save(prob: SpmvScanProblem, a_path: str, x_path: str) -> None:
         f.write(" ".join(repr(float(v)) for v in prob.x) + " \n")
 
 
-def generate(n: int, p: int, q: int, iters: int, seed: int = 0, values: np.ndarray | None = None) -> SpmvScanProblem:
+def generate(n: int, p: int, q: int, iters: int, seed: int = 0, values: np.ndarray | None = None,
+             dtype=np.float32) -> SpmvScanProblem:
     """readMM.py's generator (``aux/readMM.py:16-61``): s = 0, a sorted random
     sample of size p (its first element dropped), n; k ~ U[0, q); x ~ U(-1, 1).
     ``values`` (the matrix entries) default to U(-1, 1) -- the benchmark
-    matrices themselves are not in the reference repo."""
+    matrices themselves are not in the reference repo. ``dtype``: float32 or float64
+    (the same random stream, not rounded to float32)."""
     rng = np.random.default_rng(seed)
-    a = values.astype(np.float32) if values is not None else rng.uniform(-1, 1, n).astype(np.float32)
+    a = values.astype(dtype) if values is not None else rng.uniform(-1, 1, n).astype(dtype)
     samp = np.sort(rng.choice(n, size=p, replace=False))
     s = np.empty(p, dtype=np.int32)
     s[0] = 0
     s[1:p - 1] = samp[1:p - 1]
     s[p - 1] = n
     k = rng.integers(0, q, size=n, dtype=np.int64).astype(np.int32)
-    x = rng.uniform(-1, 1, q).astype(np.float32)
+    x = rng.uniform(-1, 1, q).astype(dtype)
     return SpmvScanProblem(a, s, k, x, iters)
 
 
@@ -123,25 +127,34 @@ class SpmvScanSolver:
     scan over the whole array, load-balanced whatever the segment lengths),
     "wave" (one wave per segment: the reference's ``fp.cu`` algorithm, made
     race-free with a DPP scan), "serial" (one lane per segment: ``fp_old.cu``).
-    The last two are GPU-only comparison variants."""
+    The last two are GPU-only comparison variants, float32 only.
 
-    def __init__(self, prob: SpmvScanProblem, device="cuda", algo: str = "lookback"):
+    ``dtype``: ``torch.float32`` or ``torch.float64``, the type the state is
+    held and every step is computed in (the problem's arrays are converted)."""
+
+    def __init__(self, prob: SpmvScanProblem, device="cuda", algo: str = "lookback",
+                 dtype: torch.dtype = torch.float32):
         if algo not in ALGOS:
             raise ValueError(f"algo must be one of {ALGOS}")
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("dtype must be torch.float32 or torch.float64")
+        if dtype == torch.float64 and algo != "lookback":
+            raise ValueError(f"algo {algo!r} is float32 only; float64 takes 'lookback'")
+        self.dtype = dtype
         self.prob = prob
         self.algo = algo
         self.device = torch.device(device)
         if algo != "lookback" and self.device.type != "cuda":
             raise ValueError(f"algo {algo!r} is a GPU kernel")
         self.offsets = torch.from_numpy(prob.s.astype(np.int32)).to(self.device)
-        x = torch.from_numpy(prob.x).to(self.device)
+        x = torch.from_numpy(prob.x).to(dtype).to(self.device)
         k = torch.from_numpy(prob.k.astype(np.int64)).to(self.device)
         self.xx = x[k].contiguous()  # pre-flattened gather (untimed, fp.cu:124-125)
         self.flags = head_flags_from_offsets(torch.from_numpy(prob.s), prob.n, self.device)
-        self.a = torch.from_numpy(prob.a.copy()).to(self.device)
+        self.a = torch.from_numpy(prob.a.copy()).to(dtype).to(self.device)
 
     def reset(self) -> None:
-        self.a.copy_(torch.from_numpy(self.prob.a))
+        self.a.copy_(torch.from_numpy(self.prob.a).to(self.dtype))
 
     def step(self) -> None:
         if self.algo != "lookback":
@@ -207,12 +220,14 @@ def errors(ref: np.ndarray, b: np.ndarray) -> dict:
 
 
 def run_fp(a_path: str, x_path: str, cpu_check: bool = False, device: str | None = None,
-           out_path: str = "b.txt", algo: str = "lookback", graph: bool = False) -> dict:
-    """The ``./fp a.txt x.txt [check]`` driver (``fp.cu:74-216``)."""
+           out_path: str = "b.txt", algo: str = "lookback", graph: bool = False, double: bool = False) -> dict:
+    """The ``./fp a.txt x.txt [check]`` driver (``fp.cu:74-216``). ``double``:
+    load, iterate and write in float64 (``b.txt`` and ``b_cpu.txt`` then carry
+    17 significant digits, not the reference format's 6)."""
     device = device or ("cuda" if torch.cuda.is_available() else "cpu")
-    prob = load(a_path, x_path)
+    prob = load(a_path, x_path, dtype=np.float64 if double else np.float32)
     print(f"\nDim of a: {prob.n}\nDim of x: {prob.q}\nDim of s: {prob.p}\n# of iters: {prob.iters}\n")
-    sol = SpmvScanSolver(prob, device, algo)
+    sol = SpmvScanSolver(prob, device, algo, dtype=torch.float64 if double else torch.float32)
     sol.run(1)  # warm-up (code object load), then restore a
     sol.reset()
     runner = None
@@ -231,10 +246,11 @@ def run_fp(a_path: str, x_path: str, cpu_check: bool = False, device: str | None
     print(f"The running time of my code for {prob.iters} iterations is: {t.ms:g} milliseconds.\n")
     b = sol.a.cpu().numpy()
     res = {"ms": t.ms, "n": prob.n, "p": prob.p, "N": prob.iters,
-           "GBps": 12.0 * prob.n * prob.iters / t.ms / 1e6}
+           "GBps": (24.0 if double else 12.0) * prob.n * prob.iters / t.ms / 1e6}  # read a, xx, write a
+    digits = 17 if double else None
     if cpu_check:
         ref = reference_solution(prob)
         res.update(errors(ref, b))
-        write_vector("b_cpu.txt", ref.astype(np.float32))
-    write_vector(out_path, b)
+        write_vector("b_cpu.txt", ref if double else ref.astype(np.float32), digits)
+    write_vector(out_path, b, digits)
     return res

@@ -92,7 +92,7 @@ def _(x, exclusive=False):
 
 @torch.library.custom_op(f"{NS}::segmented_scan", mutates_args=())
 def segmented_scan(x: Tensor, flags: Tensor) -> Tensor:
-    """segmented_scan(Tensor x, Tensor flags) -> Tensor"""
+    """segmented_scan(Tensor x, Tensor flags) -> Tensor   (float32 / int64 / float64)"""
     return _fresh(_scan.segmented_scan(x.contiguous(), flags.contiguous()), x)
 
 

@@ -11,7 +11,8 @@
 * :func:`segmented_scan` -- inclusive, head-flag segmented scan (Lecture21;
   nvr-2008-003), optionally fused with an element-wise multiply: the final
   project's ``a *= x[k]; b = segscan(a)`` step (``hw/hw_final/programming/
-  fp.cu:168-185``) in one pass.
+  fp.cu:168-185``) in one pass. float32, and int64 / float64
+  (``csrc/hip/segscan64.hip``).
 
 CPU tensors use the OpenMP oracles in ``csrc/cpu/scan_cpu.cpp``.
 """
@@ -110,15 +111,16 @@ def scan64_launch_info(n: int, device: torch.device | str = "cuda") -> dict:
     return dict(zip(keys, (int(v) for v in info)))
 
 
-def _lookback64_ws(x: torch.Tensor) -> tuple[torch.Tensor, int]:
+def _lookback64_ws(x: torch.Tensor, tile: int = TILE64, family: str = "lookback64") -> tuple[torch.Tensor, int]:
     """Descriptor array and epoch of a 64-bit look-back launch. As
     :func:`_lookback_ws`, but an array and an epoch count of their own per
     (device, stream): a slot is two 8-byte granules there (twice the bytes),
     and a 32-bit and a 64-bit scan issued back to back on one stream never
-    read each other's words."""
-    tiles = (x.numel() + TILE64 - 1) // TILE64
-    nbytes = 32 * tiles + 32 * (tiles // 64 + 1) + 64  # scan64.hip lb64_ws_bytes
-    k = (f"lookback64:{_ext.stream_ptr(x.device)}", x.device.index)
+    read each other's words. ``family`` keeps the plain and the segmented
+    64-bit scans (tiles of ``tile`` elements) apart in the same way."""
+    tiles = (x.numel() + tile - 1) // tile
+    nbytes = 32 * tiles + 32 * (tiles // 64 + 1) + 64  # scan64.h lb64_ws_bytes
+    k = (f"{family}:{_ext.stream_ptr(x.device)}", x.device.index)
     t = _ws_cache.get(k)
     if t is None or t.numel() < nbytes:
         t = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=x.device)
@@ -311,10 +313,82 @@ def head_flags_from_offsets(s: torch.Tensor, n: int, device=None, bitmask: bool 
     return f.to(device) if device is not None else f
 
 
+_ext.proto(_ext.HIP_PROTOS, "cme_segscan64", "ppppiqipup")
+_ext.proto(_ext.HIP_PROTOS, "cme_spmv_scan_run64", "pppqipp")
+_ext.proto(_ext.HIP_PROTOS, "cme_spmv_scan64_ws_bytes", "qp")
+_ext.proto(_ext.HIP_PROTOS, "cme_segscan64_info", "qp")
+_ext.proto(_ext.CPU_PROTOS, "cme_cpu_segscan64", "ppppiqi")
+
+SEGTILE64 = 4096  # elements per tile of the 64-bit segmented scan (scan64.h kSegScan64Tile)
+_SEGSCAN_DTYPES = (torch.float32, torch.int64, torch.float64)
+
+
+def segscan64_launch_info(n: int, device: torch.device | str = "cuda") -> dict:
+    """How a 64-bit :func:`segmented_scan` of ``n`` elements is launched on
+    ``device``: ``tile`` (elements), ``tiles``, ``workgroups`` (the persistent,
+    co-resident grid), ``blocks_per_cu``, ``ws_bytes``."""
+    import ctypes
+
+    info = (ctypes.c_longlong * 5)()
+    with torch.cuda.device(torch.device(device)):
+        _ext.call_hip("cme_segscan64_info", n, ctypes.addressof(info))
+    return dict(zip(("tile", "tiles", "workgroups", "blocks_per_cu", "ws_bytes"), (int(v) for v in info)))
+
+
+def _run64_ws(x: torch.Tensor) -> torch.Tensor:
+    """Descriptors of the float64 :func:`spmv_scan_run`, which zeroes them
+    natively and numbers its own epochs (see :func:`_run_ws`)."""
+    import ctypes
+
+    nbytes = ctypes.c_longlong(0)
+    _ext.call_hip("cme_spmv_scan64_ws_bytes", x.numel(), ctypes.addressof(nbytes))
+    return workspace(x.device, nbytes.value, f"lookback-run64:{_ext.stream_ptr(x.device)}")
+
+
+def _segscan64(x: torch.Tensor, flags: torch.Tensor, out: torch.Tensor | None, mul: torch.Tensor | None) -> torch.Tensor:
+    for name, t in (("mul", mul), ("out", out)):
+        if t is not None and (t.dtype != x.dtype or t.numel() != x.numel() or t.device != x.device
+                              or not t.is_contiguous()):
+            raise ValueError(f"segmented_scan: {name} must be a contiguous tensor of x's dtype, length and device")
+    if flags.dtype not in (torch.uint8, torch.int32):
+        raise TypeError(f"segmented_scan: flags must be uint8 (one per element) or int32 bitmask words, not {flags.dtype}")
+    if flags.device != x.device or not flags.is_contiguous():
+        raise ValueError("segmented_scan: flags must be contiguous and on x's device")
+    n = x.numel()
+    mode = 0 if flags.dtype == torch.uint8 else 1
+    if flags.numel() < (n if mode == 0 else (n + 31) // 32):
+        raise ValueError("segmented_scan: flags are shorter than x")
+    if not x.is_contiguous():
+        x = x.contiguous()
+    out = torch.empty_like(x) if out is None else out
+    mp = mul.data_ptr() if mul is not None else None
+    if x.is_cuda:
+        _check_lookback(x, before=True)
+        # descriptors and epochs apart from the 32-bit scans' and the plain 64-bit scan's
+        ws, epoch = _lookback64_ws(x, SEGTILE64, "segscan64")
+        _ext.call_hip("cme_segscan64", x.data_ptr(), mp, out.data_ptr(), flags.data_ptr(), mode, n, _DT64[x.dtype],
+                      ws.data_ptr(), epoch, _ext.stream_ptr(x.device))
+        _check_lookback(x)
+    else:
+        _ext.call_cpu("cme_cpu_segscan64", x.data_ptr(), mp, out.data_ptr(), flags.data_ptr(), mode, n, _DT64[x.dtype])
+    return out
+
+
 def segmented_scan(x: torch.Tensor, flags: torch.Tensor, out: torch.Tensor | None = None,
                    mul: torch.Tensor | None = None) -> torch.Tensor:
-    """Inclusive segmented sum scan of float32 ``x`` (optionally ``x*mul``).
-    ``flags``: uint8 per element (0/1) or int32 bitmask words."""
+    """Inclusive segmented sum scan of float32, int64 or float64 ``x``
+    (optionally of ``x * mul``). ``flags``: uint8 per element (non-zero: a
+    segment head) or int32 bitmask words (bit ``i % 32`` of word ``i // 32``);
+    element 0 starts a segment whether or not its flag is set.
+
+    ``mul`` and ``out`` have ``x``'s dtype, length and device; ``out`` may be
+    ``x``. int64 sums wrap modulo 2^64. 64-bit data need only be 8-byte aligned
+    (``x[1:]`` is fine). Any other dtype raises a ``TypeError``."""
+    if x.dtype not in _SEGSCAN_DTYPES:
+        raise TypeError(f"segmented_scan: {x.dtype} is not supported; x must be torch.float32, torch.int64 or "
+                        "torch.float64")
+    if x.dtype in _DT64:
+        return _segscan64(x, flags, out, mul)
     out = torch.empty_like(x) if out is None else out
     n = x.numel()
     mode = 0 if flags.dtype == torch.uint8 else 1
@@ -331,14 +405,27 @@ def segmented_scan(x: torch.Tensor, flags: torch.Tensor, out: torch.Tensor | Non
 
 
 def spmv_scan_run(a: torch.Tensor, xx: torch.Tensor, flags: torch.Tensor, iters: int) -> torch.Tensor:
-    """``iters`` in-place steps ``a <- segscan(a * xx)`` (bitmask heads): one
-    descriptor memset + one kernel per step, no host synchronisation."""
+    """``iters`` in-place steps ``a <- segscan(a * xx)`` (bitmask heads) of
+    float32 or float64 ``a`` / ``xx``, without host synchronisation: one
+    persistent launch per 64 steps, with a descriptor set per step
+    (``csrc/hip/scan.hip``, ``csrc/hip/segscan64.hip``)."""
+    if a.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"spmv_scan_run: {a.dtype} is not supported; a must be torch.float32 or torch.float64")
+    if xx.dtype != a.dtype or xx.numel() != a.numel() or xx.device != a.device:
+        raise ValueError("spmv_scan_run: xx must have a's dtype, length and device")
     if not a.is_cuda:
         for _ in range(iters):
             segmented_scan(a, flags, out=a, mul=xx)
         return a
     assert flags.dtype == torch.int32, "bitmask flags expected"
     _check_lookback(a, before=True)
+    if a.dtype == torch.float64:
+        if not (a.is_contiguous() and xx.is_contiguous() and flags.is_contiguous()):
+            raise ValueError("spmv_scan_run: a, xx and flags must be contiguous")
+        _ext.call_hip("cme_spmv_scan_run64", a.data_ptr(), xx.data_ptr(), flags.data_ptr(), a.numel(), iters,
+                      _run64_ws(a).data_ptr(), _ext.stream_ptr(a.device))
+        _check_lookback(a)
+        return a
     _ext.call_hip("cme_spmv_scan_run", a.data_ptr(), xx.data_ptr(), flags.data_ptr(), a.numel(), iters,
                   _run_ws(a).data_ptr(), _ext.stream_ptr(a.device))
     _check_lookback(a)

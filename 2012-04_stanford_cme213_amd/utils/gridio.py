@@ -47,11 +47,17 @@ def write_grid(path: str, a: np.ndarray, extra_endl: bool = True) -> None:
     _ext.call_cpu(name, path.encode(), a.ctypes.data, a.shape[1], a.shape[0], a.shape[1], int(extra_endl))
 
 
-def write_vector(path: str, v: np.ndarray) -> None:
-    """``ofs << v[i] << " "`` for every element (the b.txt format)."""
+def write_vector(path: str, v: np.ndarray, digits: int | None = None) -> None:
+    """``ofs << v[i] << " "`` for every element (the b.txt format): 6
+    significant digits. ``digits`` asks for that many instead (``%.<digits>g``;
+    17 round-trips a float64)."""
     from .. import _ext
 
     v = np.ascontiguousarray(v)
+    if digits is not None:
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        _ext.call_cpu("cme_cpu_write_vec_digits_f64", path.encode(), v.ctypes.data, v.size, int(digits))
+        return
     if v.dtype not in (np.float32, np.float64):
         v = v.astype(np.float64)
     name = "cme_cpu_write_vec_f32" if v.dtype == np.float32 else "cme_cpu_write_vec_f64"
@@ -65,6 +71,7 @@ def _register() -> None:
     _ext.proto(_ext.CPU_PROTOS, "cme_cpu_write_grid_f64", "spiiii")
     _ext.proto(_ext.CPU_PROTOS, "cme_cpu_write_vec_f32", "spq")
     _ext.proto(_ext.CPU_PROTOS, "cme_cpu_write_vec_f64", "spq")
+    _ext.proto(_ext.CPU_PROTOS, "cme_cpu_write_vec_digits_f64", "spqi")
 
 
 _register()

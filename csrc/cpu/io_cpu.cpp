@@ -35,15 +35,19 @@ int write_grid(const char* path, const T* data, int pitch, int rows, int cols, i
     return std::fclose(f) == 0 ? 0 : 1;
 }
 
+// digits <= 0: "%g " (6 significant digits, the reference's format);
+// otherwise "%.<digits>g " (17 round-trips a double).
 template <typename T>
-int write_vec(const char* path, const T* data, long long n) {
+int write_vec(const char* path, const T* data, long long n, int digits = 0) {
+    if (digits > 40) return 1;
     FILE* f = std::fopen(path, "w");
     if (!f) return 1;
     char tmp[64];
     std::vector<char> buf;
     buf.reserve(1 << 20);
     for (long long i = 0; i < n; ++i) {
-        int k = std::snprintf(tmp, sizeof(tmp), "%g ", (double)data[i]);
+        int k = digits > 0 ? std::snprintf(tmp, sizeof(tmp), "%.*g ", digits, (double)data[i])
+                           : std::snprintf(tmp, sizeof(tmp), "%g ", (double)data[i]);
         buf.insert(buf.end(), tmp, tmp + k);
         if (buf.size() > (1 << 20) - 64) {
             std::fwrite(buf.data(), 1, buf.size(), f);
@@ -64,3 +68,6 @@ CME_CPU_EXPORT int cme_cpu_write_grid_f64(const char* path, const double* d, int
 }
 CME_CPU_EXPORT int cme_cpu_write_vec_f32(const char* path, const float* d, long long n) { return write_vec(path, d, n); }
 CME_CPU_EXPORT int cme_cpu_write_vec_f64(const char* path, const double* d, long long n) { return write_vec(path, d, n); }
+CME_CPU_EXPORT int cme_cpu_write_vec_digits_f64(const char* path, const double* d, long long n, int digits) {
+    return write_vec(path, d, n, digits);
+}

@@ -116,3 +116,42 @@ CME_CPU_EXPORT int cme_cpu_segscan(const float* in, const float* xmul, float* ou
     }
     return 0;
 }
+
+namespace {
+
+template <typename T>
+void segscan64_impl(const T* in, const T* xmul, T* out, const void* flags, int mode, long long n) {
+    auto head = [&](long long i) -> bool {
+        if (mode == 0) return ((const uint8_t*)flags)[i] != 0;
+        return (((const uint32_t*)flags)[i >> 5] >> (i & 31)) & 1u;
+    };
+    std::vector<long long> starts;
+    starts.push_back(0);  // element 0 starts a segment whether or not its flag is set
+    for (long long i = 1; i < n; ++i)
+        if (head(i)) starts.push_back(i);
+    starts.push_back(n);
+    const long long ns = (long long)starts.size() - 1;
+#pragma omp parallel for schedule(dynamic, 64)
+    for (long long sgi = 0; sgi < ns; ++sgi) {
+        T run = T(0);
+        for (long long i = starts[sgi]; i < starts[sgi + 1]; ++i) {
+            const T v = xmul ? in[i] * xmul[i] : in[i];
+            run = (i == starts[sgi]) ? v : run + v;
+            out[i] = run;
+        }
+    }
+}
+
+}  // namespace
+
+// The same for 8-byte elements: dtype 3 int64 (summed as uint64: wraps modulo
+// 2^64), 4 float64. Serial within a segment, parallel across segments; out
+// may be in.
+CME_CPU_EXPORT int cme_cpu_segscan64(const void* in, const void* xmul, void* out, const void* flags, int mode,
+                                     long long n, int dtype) {
+    if (n <= 0) return 0;
+    if (dtype == 3) segscan64_impl((const uint64_t*)in, (const uint64_t*)xmul, (uint64_t*)out, flags, mode, n);
+    else if (dtype == 4) segscan64_impl((const double*)in, (const double*)xmul, (double*)out, flags, mode, n);
+    else return 1;
+    return 0;
+}

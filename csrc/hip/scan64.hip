@@ -37,85 +37,8 @@ constexpr int kRowElems = kWave * 2;           // 128: one 16-B vector per lane
 // hand-off, and larger tiles mean fewer hand-offs per byte.
 constexpr int kLbRows = kScan64LbRows;
 
-template <typename T>
-struct Vec2 {
-    T x, y;
-};
-
-// 16-B vector of two elements that is only 8-byte aligned: x[1:] of a 64-bit
-// tensor is a legal operand. Global dwordx4 accesses need dword alignment
-// only, so the compiler still emits one 16-B load / store per lane.
-template <typename T>
-struct V2 {
-    typedef T aligned16 __attribute__((ext_vector_type(2)));
-    typedef aligned16 type __attribute__((aligned(8)));
-};
-
-template <typename T>
-__device__ __forceinline__ Vec2<T> load_v2(const T* p, long long i, long long n, T id) {
-    Vec2<T> r;
-    if (i + 1 < n) {
-        const typename V2<T>::aligned16 v = *reinterpret_cast<const typename V2<T>::type*>(p + i);
-        r.x = v.x;
-        r.y = v.y;
-    } else {
-        r.x = i < n ? p[i] : id;
-        r.y = id;
-    }
-    return r;
-}
-
-template <bool NTS = false, typename T>
-__device__ __forceinline__ void store_v2(T* p, long long i, long long n, const Vec2<T>& r) {
-    if (i + 1 < n) {
-        const typename V2<T>::aligned16 v = {r.x, r.y};
-        if constexpr (NTS)  // write-once output: stream it past the caches
-            __builtin_nontemporal_store(v, reinterpret_cast<typename V2<T>::type*>(p + i));
-        else
-            *reinterpret_cast<typename V2<T>::type*>(p + i) = v;
-    } else if (i < n) {
-        p[i] = r.x;
-    }
-}
-
-// ------------------------------------------------- 64-bit look-back descriptors
-// A slot is two naturally aligned 8-byte granules, each {(epoch << 8) | status
-// : 32, 32 value bits}: the low half first, then the high half. Each granule is
-// ONE relaxed agent-scope atomic store and is read by relaxed agent-scope
-// atomic loads (lookback.h lb_publish / lb_poll); nothing relies on a 16-byte
-// access being single-copy atomic. Slots are WRITE-ONCE per epoch (the
-// two-level layout: agg, inc, gagg, ginc), so a half that carries the
-// launch's epoch holds its final bits, and a slot is valid exactly when both
-// halves carry the launch's epoch and the same non-zero status; until then
-// the waiter keeps polling.
-struct Lb64 {
-    uint64_t *agg, *inc, *gagg, *ginc;
-};
-inline size_t lb64_ws_bytes(long long tiles) { return 16 + 32 * (size_t)tiles + 32 * (size_t)((tiles + 63) / 64); }
-__host__ __device__ inline Lb64 lb64_views(uint64_t* desc, long long tiles) {
-    const long long groups = (tiles + 63) / 64;
-    return Lb64{desc, desc + 2 * tiles, desc + 4 * tiles, desc + 4 * tiles + 2 * groups};
-}
-
-template <typename T>
-__device__ __forceinline__ void lb64_put(uint64_t* slot, T v, uint32_t epoch) {
-    const uint64_t bits = __builtin_bit_cast(uint64_t, v);
-    lb_publish(slot, kStAggregate, (uint32_t)bits, epoch);
-    lb_publish(slot + 1, kStAggregate, (uint32_t)(bits >> 32), epoch);
-}
-
-// status of a slot for this epoch (0: not published yet, or half published)
-__device__ __forceinline__ uint32_t lb64_get(uint64_t* slot, uint32_t epoch, uint64_t* bits) {
-    const uint64_t lo = lb_poll(slot), hi = lb_poll(slot + 1);
-    const uint32_t wl = (uint32_t)(lo >> 32), wh = (uint32_t)(hi >> 32);
-    *bits = (hi << 32) | (uint32_t)lo;
-    return (wl == wh && (wl >> 8) == epoch) ? (wl & 0xffu) : 0u;
-}
-
-template <typename T>
-__device__ __forceinline__ T lb64_val(uint64_t bits) {
-    return __builtin_bit_cast(T, bits);
-}
+// Vec2 / load_v2 / store_v2 and the two-granule descriptor slots (Lb64,
+// lb64_put / lb64_get) are in scan64.h, shared with segscan64.hip.
 
 // One wave: lanes l < n inspect predecessor slot base - l of (a, inc); see
 // lookback.h lb2_window (this is its unsegmented form over two-granule slots).
