@@ -42,6 +42,7 @@ _OPS = {"sum": 0, "max": 1, "min": 2}
 TILE = 4096
 TILE64 = 8192  # elements per tile of the 64-bit look-back scan (scan64.h kScan64Tile; "rts" tiles are half)
 _ALGOS64 = ("rts", "lookback")
+_VECTOR_ALGOS = ("lookback", "rts", "blelloch", "hillis")  # 32-bit: 16-byte loads and stores (the *_mlevel are scalar)
 # "auto" for int64: the look-back measured faster than reduce-then-scan at
 # both 2^25 and 2^27 elements (benchmarks/bench_primitives.py --only scan64,
 # profiles/scan64_r8.md)
@@ -91,6 +92,37 @@ def _lookback_ws(x: torch.Tensor) -> tuple[torch.Tensor, int]:
         e = 1
     _epochs[k] = e
     return t, e
+
+
+def _aligned(t: torch.Tensor, nbytes: int = 16) -> torch.Tensor:
+    """``t`` itself if its data is ``nbytes``-aligned, else a copy that is (a
+    fresh allocation). The 32-bit GPU kernels load and store whole 16-byte
+    vectors (and four uint8 flags per 4-byte load) without a scalar path, so a
+    view such as ``x[1:]`` is staged through an aligned temporary; aligned
+    operands are passed as they are."""
+    return t if t.data_ptr() % nbytes == 0 else t.clone()
+
+
+_ext.proto(_ext.HIP_PROTOS, "cme_scan32_info", "qiiip")
+_SCAN32_KINDS = {"lookback": 0, "segscan": 1}
+
+
+def scan_launch_info(n: int, kind: str = "lookback", exclusive: bool = False, device: torch.device | str = "cuda",
+                     dtype: torch.dtype = torch.float32) -> dict:
+    """How a 32-bit look-back launch of ``n`` elements is shaped on ``device``:
+    ``tile`` (elements), ``tiles``, ``workgroups`` (the persistent, co-resident
+    grid) and ``blocks_per_cu``. ``kind``: "lookback" (:func:`scan` with
+    ``algo="lookback"``; ``exclusive`` and ``dtype`` pick the kernel) or
+    "segscan" (the float32 :func:`segmented_scan`)."""
+    import ctypes
+
+    if kind not in _SCAN32_KINDS:
+        raise ValueError(f"scan_launch_info: kind {kind!r} is not one of {sorted(_SCAN32_KINDS)}")
+    info = (ctypes.c_longlong * 4)()
+    with torch.cuda.device(torch.device(device)):
+        _ext.call_hip("cme_scan32_info", n, _SCAN32_KINDS[kind], _DT_SCAN[dtype], int(exclusive),
+                      ctypes.addressof(info))
+    return dict(zip(("tile", "tiles", "workgroups", "blocks_per_cu"), (int(v) for v in info)))
 
 
 _ext.proto(_ext.HIP_PROTOS, "cme_scan64_info", "qp")
@@ -213,8 +245,10 @@ def scan(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = No
     int64 and float64 take "rts" and "lookback" only (a ``TypeError`` names
     them otherwise). int64 sums wrap modulo 2^64, as ``torch.cumsum`` and numpy
     do; a uint64 sum is the int64 sum of the same bits (``.view``). The data
-    need only be 8-byte aligned (``x[1:]`` is fine). ``out`` (same dtype and
-    length, contiguous) may be ``x`` itself for "rts" and "lookback"."""
+    need only be 8-byte aligned (``x[1:]`` is fine); a 32-bit ``x`` or ``out``
+    that is not 16-byte aligned is staged through an aligned copy on the GPU
+    (the ``_mlevel`` forms take it as it is). ``out`` (same dtype and length,
+    contiguous) may be ``x`` itself for "rts" and "lookback"."""
     if not x.is_contiguous():
         x = x.contiguous()
     if out is not None and (out.dtype != x.dtype or out.numel() != x.numel() or out.device != x.device
@@ -242,6 +276,12 @@ def scan(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = No
         else:
             _ext.call_hip("cme_scan_rts", x.data_ptr(), out.data_ptr(), n, _DT64[x.dtype], int(exclusive),
                           workspace(x.device, 8192, "rts").data_ptr(), s)
+    elif x.is_cuda and algo in _VECTOR_ALGOS and (x.data_ptr() % 16 or out.data_ptr() % 16):
+        # a view that is only 4-byte aligned (x[1:]): scan an aligned copy,
+        # into an aligned result (see _aligned)
+        staged = scan(_aligned(x), exclusive, out if out.data_ptr() % 16 == 0 else None, algo)
+        if staged is not out:
+            out.copy_(staged)
     elif x.is_cuda:
         s = _ext.stream_ptr(x.device)
         if algo == "lookback":
@@ -280,7 +320,9 @@ def reduce(x: torch.Tensor, op: str = "sum", algo: str = "vector") -> torch.Tens
     """Full reduction (``op``: "sum", "max", "min") of a float32/int32/int64/
     float64 tensor; returns a 0-d tensor on x's device. An int64 sum wraps
     modulo 2^64. ``algo="tree"`` (the lecture's LDS tree, sum only) is 32-bit
-    only and raises a ``TypeError`` for 64-bit input."""
+    only and raises a ``TypeError`` for 64-bit input. int32 sums wrap modulo
+    2^32 on both backends. A 32-bit view that is not 16-byte aligned is copied
+    for ``algo="vector"`` on the GPU."""
     x = x.contiguous()
     wide = x.dtype in _DT64
     if wide and algo != "vector":
@@ -288,6 +330,8 @@ def reduce(x: torch.Tensor, op: str = "sum", algo: str = "vector") -> torch.Tens
     dt = _DT64[x.dtype] if wide else _DT[x.dtype]
     out = torch.empty((), dtype=x.dtype, device=x.device)
     if x.is_cuda:
+        if not wide and algo == "vector":
+            x = _aligned(x)  # 16-byte loads; the LDS tree loads scalars
         part = workspace(x.device, 2048 * 4, "reduce")
         _ext.call_hip("cme_reduce", x.data_ptr(), x.numel(), dt, _OPS[op], 0 if algo == "vector" else 1,
                       part.data_ptr(), out.data_ptr(), _ext.stream_ptr(x.device))
@@ -345,7 +389,10 @@ def _run64_ws(x: torch.Tensor) -> torch.Tensor:
     return workspace(x.device, nbytes.value, f"lookback-run64:{_ext.stream_ptr(x.device)}")
 
 
-def _segscan64(x: torch.Tensor, flags: torch.Tensor, out: torch.Tensor | None, mul: torch.Tensor | None) -> torch.Tensor:
+def _segscan_args(x: torch.Tensor, flags: torch.Tensor, out: torch.Tensor | None,
+                  mul: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor, int]:
+    """The operand checks of :func:`segmented_scan` (every dtype, both
+    backends): (contiguous x, out, flag mode)."""
     for name, t in (("mul", mul), ("out", out)):
         if t is not None and (t.dtype != x.dtype or t.numel() != x.numel() or t.device != x.device
                               or not t.is_contiguous()):
@@ -360,7 +407,12 @@ def _segscan64(x: torch.Tensor, flags: torch.Tensor, out: torch.Tensor | None, m
         raise ValueError("segmented_scan: flags are shorter than x")
     if not x.is_contiguous():
         x = x.contiguous()
-    out = torch.empty_like(x) if out is None else out
+    return x, (torch.empty_like(x) if out is None else out), mode
+
+
+def _segscan64(x: torch.Tensor, flags: torch.Tensor, out: torch.Tensor | None, mul: torch.Tensor | None) -> torch.Tensor:
+    x, out, mode = _segscan_args(x, flags, out, mul)
+    n = x.numel()
     mp = mul.data_ptr() if mul is not None else None
     if x.is_cuda:
         _check_lookback(x, before=True)
@@ -383,24 +435,36 @@ def segmented_scan(x: torch.Tensor, flags: torch.Tensor, out: torch.Tensor | Non
 
     ``mul`` and ``out`` have ``x``'s dtype, length and device; ``out`` may be
     ``x``. int64 sums wrap modulo 2^64. 64-bit data need only be 8-byte aligned
-    (``x[1:]`` is fine). Any other dtype raises a ``TypeError``."""
+    (``x[1:]`` is fine); float32 views that are not 16-byte aligned, and uint8
+    flags that are not 4-byte aligned, are staged through aligned copies on the
+    GPU. Any other dtype of ``x`` raises a ``TypeError``, and so do flags that
+    are neither uint8 nor int32 (``torch.bool`` included: pass
+    ``flags.view(torch.uint8)``); flags must be contiguous, on ``x``'s device
+    and cover ``x``. A non-contiguous ``x`` is copied."""
     if x.dtype not in _SEGSCAN_DTYPES:
         raise TypeError(f"segmented_scan: {x.dtype} is not supported; x must be torch.float32, torch.int64 or "
                         "torch.float64")
     if x.dtype in _DT64:
         return _segscan64(x, flags, out, mul)
-    out = torch.empty_like(x) if out is None else out
+    x, out, mode = _segscan_args(x, flags, out, mul)
     n = x.numel()
-    mode = 0 if flags.dtype == torch.uint8 else 1
-    mp = mul.data_ptr() if mul is not None else None
     if x.is_cuda:
+        # 16-byte vector loads and stores, four uint8 flags per 4-byte load
+        # (int32 bitmask words are 4-byte aligned as they are): see _aligned
+        x, flags, dst = _aligned(x), _aligned(flags, 4), out
+        mul = _aligned(mul) if mul is not None else None
+        if out.data_ptr() % 16:
+            dst = torch.empty_like(x)
         _check_lookback(x, before=True)
         ws, epoch = _lookback_ws(x)
-        _ext.call_hip("cme_segscan", x.data_ptr(), mp, out.data_ptr(), flags.data_ptr(), mode, n, ws.data_ptr(),
-                      epoch, _ext.stream_ptr(x.device))
+        _ext.call_hip("cme_segscan", x.data_ptr(), mul.data_ptr() if mul is not None else None, dst.data_ptr(),
+                      flags.data_ptr(), mode, n, ws.data_ptr(), epoch, _ext.stream_ptr(x.device))
         _check_lookback(x)
-    else:
-        _ext.call_cpu("cme_cpu_segscan", x.data_ptr(), mp, out.data_ptr(), flags.data_ptr(), mode, n)
+        if dst is not out:
+            out.copy_(dst)
+        return out
+    _ext.call_cpu("cme_cpu_segscan", x.data_ptr(), mul.data_ptr() if mul is not None else None, out.data_ptr(),
+                  flags.data_ptr(), mode, n)
     return out
 
 
@@ -426,7 +490,14 @@ def spmv_scan_run(a: torch.Tensor, xx: torch.Tensor, flags: torch.Tensor, iters:
                       _run64_ws(a).data_ptr(), _ext.stream_ptr(a.device))
         _check_lookback(a)
         return a
-    _ext.call_hip("cme_spmv_scan_run", a.data_ptr(), xx.data_ptr(), flags.data_ptr(), a.numel(), iters,
+    if not (a.is_contiguous() and xx.is_contiguous() and flags.is_contiguous()):
+        raise ValueError("spmv_scan_run: a, xx and flags must be contiguous")
+    # 16-byte vector loads and stores: see _aligned (both copies are held until
+    # the launch is enqueued, so the workspace is never allocated over one)
+    run, xs = _aligned(a), _aligned(xx)
+    _ext.call_hip("cme_spmv_scan_run", run.data_ptr(), xs.data_ptr(), flags.data_ptr(), a.numel(), iters,
                   _run_ws(a).data_ptr(), _ext.stream_ptr(a.device))
     _check_lookback(a)
+    if run is not a:
+        a.copy_(run)
     return a

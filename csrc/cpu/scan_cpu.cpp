@@ -4,6 +4,7 @@
 #include <omp.h>
 
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "cme213/cpu_common.h"
@@ -49,6 +50,13 @@ void reduce_impl(const T* in, long long n, int op, T* out) {
 #pragma omp parallel for reduction(+ : a)
         for (long long i = 0; i < n; ++i) a += in[i];
         acc = a;
+    } else if (op == 0 && std::is_integral<T>::value) {
+        // int32 sums wrap modulo 2^32, as the GPU kernels' do: summed unsigned
+        // (a double sum cast back to int is undefined once it leaves the range)
+        uint32_t a = 0;
+#pragma omp parallel for reduction(+ : a)
+        for (long long i = 0; i < n; ++i) a += (uint32_t)in[i];
+        acc = (T)a;
     } else if (op == 0) {
         double a = 0;  // fp64 accumulation for the oracle
 #pragma omp parallel for reduction(+ : a)
@@ -70,7 +78,8 @@ void reduce_impl(const T* in, long long n, int op, T* out) {
 
 CME_CPU_EXPORT int cme_cpu_scan(const void* in, void* out, long long n, int dtype, int exclusive) {
     if (dtype == 0) scan_impl((const float*)in, (float*)out, n, exclusive);
-    else if (dtype == 1) scan_impl((const int*)in, (int*)out, n, exclusive);
+    // int32 in unsigned arithmetic too: the sum wraps modulo 2^32
+    else if (dtype == 1) scan_impl((const uint32_t*)in, (uint32_t*)out, n, exclusive);
     else if (dtype == 2) scan_impl((const uint32_t*)in, (uint32_t*)out, n, exclusive);
     // int64 in unsigned arithmetic: the sum wraps modulo 2^64 (signed overflow is undefined)
     else if (dtype == 3) scan_impl((const uint64_t*)in, (uint64_t*)out, n, exclusive);

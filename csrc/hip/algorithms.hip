@@ -494,9 +494,13 @@ int select_impl(const U* x, const uint8_t* flags, long long n, int pred, U value
                                value, invert, (int)ntiles, desc, timeout, out, count_out);
         CME_LAUNCH_STATUS();
     }
+    // counts, offsets and the scan's partials each start 16-byte aligned (the
+    // scan moves 16-B vectors and refuses operands that are not):
+    // cme_select_ws_bytes covers the padding of at most 3 ints each
+    const long long ntiles4 = (ntiles + 3) / 4 * 4;
     int* counts = ws;
-    int* offsets = ws + ntiles;
-    void* scan_ws = ws + 2 * ntiles;
+    int* offsets = ws + ntiles4;
+    void* scan_ws = ws + 2 * ntiles4;
     hipLaunchKernelGGL(select_count_kernel<U>, dim3((unsigned)ntiles), dim3(kThreads), 0, s, x, flags, n, pred, value,
                        invert, counts);
     CME_TRY(hipGetLastError());

@@ -46,10 +46,28 @@ CME_EXPORT int cme_lookback_timeout_word(void** host_word) {
 }
 
 
+namespace {
+// The 32-bit kernels load and store unguarded 16-B vectors (load_v4 /
+// store_v4, the non-temporal stores), so their operands must be 16-byte
+// aligned: ops/scan.py stages a tensor view that is not (x[1:]) through an
+// aligned temporary, and the entry points refuse one rather than launch on it.
+// A null pointer (no xmul) passes.
+inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
+// Largest co-resident grid of cme_segscan (and the cme_scan32_info query).
+int segscan_grid_cap() {
+    static int bpc = persistent_blocks_per_cu(segscan_kernel<1, true, 4, false, true>, kScanThreads);
+    return device_cu_count() * bpc;
+}
+}  // namespace
+
 // Reduce-then-scan (deterministic). dtype: 0 f32, 1 i32, 2 u32, 3 i64, 4 f64
 // (scan64.hip). ws: >= 8 * 1024 bytes.
 CME_EXPORT int cme_scan_rts(const void* in, void* out, long long n, int dtype, int exclusive, void* ws, void* stream) {
     hipStream_t s = as_stream(stream);
+    if (dtype >= 0 && dtype <= 2 && !aligned16(in, out)) return (int)hipErrorInvalidValue;
     switch (dtype) {
         case 0: return launch_rts<float>((const float*)in, (float*)out, n, exclusive, ws, s);
         case 1: return launch_rts<int>((const int*)in, (int*)out, n, exclusive, ws, s);
@@ -66,6 +84,7 @@ CME_EXPORT int cme_scan_rts(const void* in, void* out, long long n, int dtype, i
 CME_EXPORT int cme_scan_tree(const void* in, void* out, long long n, int dtype, int algo, int exclusive, void* ws,
                              void* stream) {
     hipStream_t s = as_stream(stream);
+    if (!aligned16(in, out)) return (int)hipErrorInvalidValue;
     switch (dtype) {
         case 0: return launch_tree_rts<float>((const float*)in, (float*)out, n, algo, exclusive, ws, s);
         case 1: return launch_tree_rts<int>((const int*)in, (int*)out, n, algo, exclusive, ws, s);
@@ -80,6 +99,7 @@ CME_EXPORT int cme_scan_tree(const void* in, void* out, long long n, int dtype, 
 CME_EXPORT int cme_scan(const void* in, void* out, long long n, int dtype, int exclusive, void* ws, unsigned epoch,
                         void* stream) {
     hipStream_t s = as_stream(stream);
+    if (dtype >= 0 && dtype <= 2 && !aligned16(in, out)) return (int)hipErrorInvalidValue;
     switch (dtype) {
         case 0: return launch_scan<float>((const float*)in, (float*)out, n, exclusive, ws, s, epoch);
         case 1: return launch_scan<int>((const int*)in, (int*)out, n, exclusive, ws, s, epoch);
@@ -88,6 +108,33 @@ CME_EXPORT int cme_scan(const void* in, void* out, long long n, int dtype, int e
         case 4: return scan64_lookback(in, out, n, dtype, exclusive, ws, s, epoch);
         default: return (int)hipErrorInvalidValue;
     }
+}
+
+// How the 32-bit look-back scans of n elements are launched on the current
+// device, by the launchers' own expressions. kind 0: cme_scan (dtype 0 / 1 / 2,
+// exclusive); kind 1: cme_segscan. info: tile (elements), tiles, workgroups
+// (the persistent, co-resident grid), blocks per CU.
+CME_EXPORT int cme_scan32_info(long long n, int kind, int dtype, int exclusive, long long* info) {
+    long long tile;
+    int cap;
+    if (kind == 0) {
+        tile = kLbTile;
+        if (dtype == 0) cap = scan32_grid_cap<float>(exclusive);
+        else if (dtype == 1) cap = scan32_grid_cap<int>(exclusive);
+        else if (dtype == 2) cap = scan32_grid_cap<uint32_t>(exclusive);
+        else return (int)hipErrorInvalidValue;
+    } else if (kind == 1) {
+        tile = kScanTile;
+        cap = segscan_grid_cap();
+    } else {
+        return (int)hipErrorInvalidValue;
+    }
+    const long long tiles = n > 0 ? (n + tile - 1) / tile : 0;
+    info[0] = tile;
+    info[1] = tiles;
+    info[2] = tiles < cap ? tiles : cap;
+    info[3] = cap / device_cu_count();
+    return 0;
 }
 
 CME_EXPORT long long cme_scan_ws_bytes(long long n) { return (long long)lb2_ws_bytes((n + kScanTile - 1) / kScanTile); }
@@ -129,6 +176,7 @@ CME_EXPORT int cme_reduce(const void* in, long long n, int dtype, int op, int al
     hipStream_t s = as_stream(stream);
     const int grid = 1024;
     if (dtype == 3 || dtype == 4) return algo == 0 ? reduce64(in, n, dtype, op, part, out, s) : (int)hipErrorInvalidValue;
+    if (algo == 0 && !aligned16(in)) return (int)hipErrorInvalidValue;  // the LDS tree (algo 1) loads scalars
 #define RED(T, OP)                                                                                              \
     hipLaunchKernelGGL((reduce_partial_kernel<T, OP>), dim3(grid), dim3(256), 0, s, (const T*)in, n, (T*)part, OP()); \
     hipLaunchKernelGGL((reduce_final_kernel<T, OP>), dim3(1), dim3(1024), 0, s, (const T*)part, grid, (T*)out, OP());
@@ -166,9 +214,10 @@ CME_EXPORT int cme_segscan(const float* in, const float* xmul, float* out, const
                            long long n, void* ws, unsigned epoch, void* stream) {
     hipStream_t s = as_stream(stream);
     if (n <= 0) return 0;
+    // flags: four uint8 per 4-byte load, or the 4-byte bitmask words
+    if (!aligned16(in, xmul, out) || (uintptr_t)flags % 4 != 0) return (int)hipErrorInvalidValue;
     const int tiles = (int)((n + kScanTile - 1) / kScanTile);
-    static int bpc = persistent_blocks_per_cu(segscan_kernel<1, true, 4, false, true>, kScanThreads);
-    const int grid = tiles < device_cu_count() * bpc ? tiles : device_cu_count() * bpc;
+    const int grid = tiles < segscan_grid_cap() ? tiles : segscan_grid_cap();
     unsigned* timeout = lb_host_timeout();
     if (!timeout) return (int)hipErrorOutOfMemory;
     uint64_t* desc = lb_descriptors(ws);
@@ -199,6 +248,7 @@ CME_EXPORT int cme_segscan(const float* in, const float* xmul, float* out, const
 CME_EXPORT int cme_spmv_scan_run(float* a, const float* xx, const uint32_t* flags, long long n, int iters, void* ws,
                                  void* stream) {
     if (n <= 0 || iters <= 0) return 0;
+    if (!aligned16(a, xx)) return (int)hipErrorInvalidValue;
     const long long tiles = (n + 4095) / 4096;
     const bool multi = cme::tune_get(cme::kTuneSpmvScanMulti) != 0;  // 0: one launch per step (the round-2 path)
     static int bpc = persistent_blocks_per_cu(segscan_kernel<1, true, 4, true, true>, kScanThreads);

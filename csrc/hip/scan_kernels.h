@@ -832,8 +832,9 @@ __global__ __launch_bounds__(kScanThreads) void segscan_kernel(const float* __re
         }
         uint32_t f4;
         if constexpr (MODE == 0) {
-            const uint32_t w = raw[k].fw;
-            f4 = (w & 1u) | ((w >> 7) & 2u) | ((w >> 14) & 4u) | ((w >> 21) & 8u);
+            const uint32_t w = raw[k].fw;  // a head is any non-zero byte (2 or 0x80 as much as 1)
+            f4 = ((w & 0xffu) ? 1u : 0u) | ((w & 0xff00u) ? 2u : 0u) | ((w & 0xff0000u) ? 4u : 0u) |
+                 ((w & 0xff000000u) ? 8u : 0u);
         } else {
             f4 = (raw[k].fw >> (i & 31)) & 0xfu;
         }
@@ -947,15 +948,24 @@ __global__ __launch_bounds__(kScanThreads) void segscan_kernel(const float* __re
 // epoch 0: zero the descriptors first (one memset); epoch e > 0: the caller
 // zeroed `ws` once and gives every launch a new epoch (stale descriptors of
 // earlier launches never match), so repeated scans skip the memset.
+constexpr long long kLbTile = 1024LL * kLbRows;  // elements per tile of the production look-back scan
+
+// Largest co-resident grid of the production look-back scan (launch_scan and
+// the cme_scan32_info query).
 template <typename T>
-int launch_scan(const T* in, T* out, long long n, int exclusive, void* ws, hipStream_t s, uint32_t epoch) {
-    if (n <= 0) return 0;
-    const int tiles = (int)((n + 1024LL * kLbRows - 1) / (1024LL * kLbRows));
+int scan32_grid_cap(int exclusive) {
     static int bpc_e = persistent_blocks_per_cu(
         scan_lookback_kernel<T, true, kLbRows, true, kLbMode, false, kLbPf, kLbNt>, kScanThreads);
     static int bpc_i = persistent_blocks_per_cu(
         scan_lookback_kernel<T, false, kLbRows, true, kLbMode, false, kLbPf, kLbNt>, kScanThreads);
-    const int cap = device_cu_count() * (exclusive ? bpc_e : bpc_i);
+    return device_cu_count() * (exclusive ? bpc_e : bpc_i);
+}
+
+template <typename T>
+int launch_scan(const T* in, T* out, long long n, int exclusive, void* ws, hipStream_t s, uint32_t epoch) {
+    if (n <= 0) return 0;
+    const int tiles = (int)((n + kLbTile - 1) / kLbTile);
+    const int cap = scan32_grid_cap<T>(exclusive);
     const int grid = tiles < cap ? tiles : cap;
     unsigned* timeout = lb_host_timeout();
     if (!timeout) return (int)hipErrorOutOfMemory;

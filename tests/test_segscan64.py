@@ -332,6 +332,41 @@ def test_segscan_8_byte_aligned_views_gpu(gpu, kind, n, mode):
     assert not lookback_timed_out(gpu)
 
 
+def _case_poison_float64(dev):
+    """An inf at the head and a NaN at the end of ONE segment, which ends at a
+    lane-vector, wave-row, wave, tile or group boundary: every other segment,
+    before and after, keeps its exact bits (the float32 twin is in
+    test_segscan32.py)."""
+    from scan_util import seg_exact_oracle
+
+    n = 64 * T + T + 1
+    x = _x("f64_exact", n)
+    for end in (T + 8, T + 256, T + 1024, 2 * T, 64 * T):
+        f = _heads("rand5000", n)
+        f[end - 5:end + 1] = [1, 0, 0, 0, 0, 1]  # the poisoned segment [end - 5, end); the next starts at the boundary
+        want = seg_exact_oracle(x, f, 2.0 ** 44)
+        xp = x.copy()
+        xp[end - 5] = np.inf
+        xp[end - 1] = np.nan
+        for mode in MODES:
+            fl = torch.from_numpy(f if mode == "u8" else np.packbits(np.pad(f, (0, -n % 32)), bitorder="little")
+                                  .view(np.int32).copy()).to(dev)
+            y = segmented_scan(torch.from_numpy(xp).to(dev), fl).cpu().numpy()
+            assert np.all(np.isinf(y[end - 5:end - 1])) and np.isnan(y[end - 1]), (end, mode)
+            assert np.array_equal(_bits(y[:end - 5]), _bits(want[:end - 5])), (end, mode)
+            assert np.array_equal(_bits(y[end:]), _bits(want[end:])), (end, mode)
+
+
+@pytest.mark.gpu
+def test_segscan_float64_poison_stays_in_its_segment_gpu(gpu):
+    _case_poison_float64(gpu)
+    assert not lookback_timed_out(gpu)
+
+
+def test_segscan_float64_poison_stays_in_its_segment_cpu():
+    _case_poison_float64(CPU)
+
+
 # ------------------------------------------------------------- look-back state
 def _rand_heads(gen, shape) -> torch.Tensor:
     return (torch.rand(shape, generator=gen) < 0.001).to(torch.uint8)
