@@ -50,8 +50,7 @@ _ext.proto(_ext.CPU_PROTOS, "cme_cpu_arg_reduce", "pqiipp")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_inner_product", "ppqip")
 
 _SEARCH_DT = {torch.float32: 0, torch.int32: 1, torch.uint32: 2, torch.int64: 3, torch.float64: 4}
-_RED_DT = {torch.float32: 0, torch.int32: 1, torch.float64: 4}
-_RED_DT_CPU = {torch.float32: 0, torch.int32: 1, torch.int64: 3, torch.float64: 4}
+_RED_DT = {torch.float32: 0, torch.int32: 1, torch.int64: 3, torch.float64: 4}
 _OPS = {"sum": 0, "max": 1, "min": 2}
 _PRED = {"flags": 0, "neq": 1, "head": 2}
 _TILE = 4096  # kTile in algorithms.hip
@@ -79,6 +78,22 @@ def _workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
     return t
 
 
+def _dtype_code(table: dict, t: torch.Tensor, what: str) -> int:
+    if t.dtype not in table:
+        names = ", ".join(str(d).split(".")[-1] for d in table)
+        raise TypeError(f"{what}: unsupported dtype {t.dtype} (takes {names})")
+    return table[t.dtype]
+
+
+def _flag_bytes(flags: torch.Tensor) -> torch.Tensor:
+    """uint8 flags for the kernels, which test every byte against zero: bool
+    and uint8 as they are, every other dtype as ``flags != 0`` (256 and 0.5
+    are set flags; a cast to uint8 would clear them)."""
+    if flags.dtype == torch.uint8:
+        return flags
+    return (flags if flags.dtype == torch.bool else flags != 0).view(torch.uint8)
+
+
 def _esize(x: torch.Tensor) -> int:
     e = x.element_size()
     if e not in (1, 4, 8):
@@ -102,7 +117,7 @@ def _select(x: torch.Tensor, flags: torch.Tensor | None, pred: str, value=0, inv
         flags = flags.contiguous().view(-1)
         if flags.numel() != n:
             raise ValueError("flags must match x")
-        flags = flags.view(torch.uint8) if flags.dtype == torch.bool else flags.to(torch.uint8)
+        flags = _flag_bytes(flags)
     out = torch.empty(n, dtype=torch.int64 if mode == 1 else x.dtype, device=x.device)
     if not x.is_cuda:
         cnt = ctypes.c_longlong(0)
@@ -127,7 +142,7 @@ def _select(x: torch.Tensor, flags: torch.Tensor | None, pred: str, value=0, inv
 
 def copy_if(x: torch.Tensor, flags: torch.Tensor, invert: bool = False) -> torch.Tensor:
     """Stable stream compaction: elements whose flag is set (``invert``: not
-    set -- ``remove_copy_if``)."""
+    set -- ``remove_copy_if``). A flag of any dtype is set iff it is ``!= 0``."""
     out, c = _select(x, flags, "flags", invert=invert)
     return out[:c]
 
@@ -139,21 +154,24 @@ def remove_value(x: torch.Tensor, value) -> torch.Tensor:
 
 
 def unique(x: torch.Tensor) -> torch.Tensor:
-    """First element of every run of equal values (``thrust::unique`` on
-    sorted input = dedup via head flags, Lecture16)."""
+    """First element of every run of bitwise equal values (``thrust::unique``
+    on sorted input = dedup via head flags, Lecture16): -0.0 and 0.0 are two
+    values, two NaNs are equal iff their bits are."""
     out, c = _select(x, None, "head")
     return out[:c]
 
 
 def run_starts(x: torch.Tensor) -> torch.Tensor:
-    """int64 indices where a new run of equal values begins."""
+    """int64 indices where a new run of bitwise equal values begins."""
     out, c = _select(x, None, "head", mode=1)
     return out[:c]
 
 
 def nonzero(flags: torch.Tensor) -> torch.Tensor:
-    """int64 indices of the set flags (stable)."""
-    out, c = _select(flags.to(torch.uint8) if flags.dtype != torch.bool else flags, flags, "flags", mode=1)
+    """int64 indices of the set flags (stable); a flag of any dtype is set iff
+    it is ``!= 0``."""
+    fb = _flag_bytes(flags.contiguous().view(-1))
+    out, c = _select(fb, fb, "flags", mode=1)
     return out[:c]
 
 
@@ -171,43 +189,47 @@ def split(x: torch.Tensor, flags: torch.Tensor) -> tuple[torch.Tensor, int]:
 
 def _search(sorted_: torch.Tensor, q: torch.Tensor, upper: bool) -> torch.Tensor:
     if sorted_.dtype != q.dtype:
-        raise TypeError("sorted and queries must share a dtype")
+        raise TypeError(f"sorted and queries must share a dtype ({sorted_.dtype} and {q.dtype})")
+    dt = _dtype_code(_SEARCH_DT, sorted_, "search")
     s, qq = sorted_.contiguous().view(-1), q.contiguous().view(-1)
     out = torch.empty(qq.numel(), dtype=torch.int64, device=q.device)
     if not sorted_.is_cuda:
-        _ext.call_cpu("cme_cpu_search", s.data_ptr(), s.numel(), qq.data_ptr(), qq.numel(), _SEARCH_DT[s.dtype],
-                      int(upper), out.data_ptr())
+        _ext.call_cpu("cme_cpu_search", s.data_ptr(), s.numel(), qq.data_ptr(), qq.numel(), dt, int(upper),
+                      out.data_ptr())
         return out
-    _ext.call_hip("cme_search", s.data_ptr(), s.numel(), qq.data_ptr(), qq.numel(), _SEARCH_DT[s.dtype], int(upper),
-                  out.data_ptr(), _ext.stream_ptr(q.device))
+    _ext.call_hip("cme_search", s.data_ptr(), s.numel(), qq.data_ptr(), qq.numel(), dt, int(upper), out.data_ptr(),
+                  _ext.stream_ptr(q.device))
     return out
 
 
 def lower_bound(sorted_: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
-    """First index i with sorted[i] >= q, per query (vectorised)."""
+    """First index i with sorted[i] >= q, per query (vectorised). The order is
+    numeric (-0.0 == 0.0); NaN keys or queries are unsupported."""
     return _search(sorted_, q, False)
 
 
 def upper_bound(sorted_: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
-    """First index i with sorted[i] > q, per query (vectorised)."""
+    """First index i with sorted[i] > q, per query (vectorised). The order is
+    numeric (-0.0 == 0.0); NaN keys or queries are unsupported."""
     return _search(sorted_, q, True)
 
 
 def segment_reduce(vals: torch.Tensor, offsets: torch.Tensor, op: str = "sum") -> torch.Tensor:
     """out[s] = op(vals[offsets[s]:offsets[s+1]]); offsets int64 (nseg + 1).
-    Empty segments give the op's identity."""
+    Empty segments give the op's identity (0; -inf / +inf; the integer's
+    lowest / largest). vals: float32, int32, int64 or float64."""
     nseg = offsets.numel() - 1
+    dt = _dtype_code(_RED_DT, vals, "segment_reduce")
     if not vals.is_cuda:
         v = vals.contiguous().view(-1)
         off = offsets.to(torch.int64).contiguous()
         out = torch.empty(nseg, dtype=v.dtype)
-        _ext.call_cpu("cme_cpu_seg_reduce", v.data_ptr(), off.data_ptr(), nseg, _RED_DT_CPU[v.dtype], _OPS[op],
-                      out.data_ptr())
+        _ext.call_cpu("cme_cpu_seg_reduce", v.data_ptr(), off.data_ptr(), nseg, dt, _OPS[op], out.data_ptr())
         return out
     v = vals.contiguous().view(-1)
     off = offsets.to(torch.int64).contiguous()
     out = torch.empty(nseg, dtype=v.dtype, device=v.device)
-    _ext.call_hip("cme_seg_reduce", v.data_ptr(), off.data_ptr(), nseg, _RED_DT[v.dtype], _OPS[op], out.data_ptr(),
+    _ext.call_hip("cme_seg_reduce", v.data_ptr(), off.data_ptr(), nseg, dt, _OPS[op], out.data_ptr(),
                   _ext.stream_ptr(v.device))
     return out
 
@@ -255,28 +277,33 @@ def counting_sort(keys: torch.Tensor, num_keys: int, values: torch.Tensor | None
 def _arg(x: torch.Tensor, is_max: bool) -> tuple[float, int]:
     if x.numel() == 0:
         raise ValueError("empty input")
+    dt = _dtype_code(_RED_DT, x, "max_element / min_element")
     xs = x.reshape(-1).contiguous()
     if not x.is_cuda:  # first index on ties, like thrust::max_element
         val = torch.empty(1, dtype=xs.dtype)
         idx = ctypes.c_longlong(0)
-        _ext.call_cpu("cme_cpu_arg_reduce", xs.data_ptr(), xs.numel(), _RED_DT_CPU[xs.dtype], int(is_max),
-                      val.data_ptr(), ctypes.addressof(idx))
+        _ext.call_cpu("cme_cpu_arg_reduce", xs.data_ptr(), xs.numel(), dt, int(is_max), val.data_ptr(),
+                      ctypes.addressof(idx))
         return val.item(), idx.value
     ov = torch.empty(1, dtype=xs.dtype, device=xs.device)
     oi = torch.empty(1, dtype=torch.int64, device=xs.device)
     ws = _workspace(xs.device, 16 * 2048)
-    _ext.call_hip("cme_arg_reduce", xs.data_ptr(), xs.numel(), _RED_DT[xs.dtype], int(is_max), ws.data_ptr(),
-                  ov.data_ptr(), oi.data_ptr(), _ext.stream_ptr(xs.device))
+    _ext.call_hip("cme_arg_reduce", xs.data_ptr(), xs.numel(), dt, int(is_max), ws.data_ptr(), ov.data_ptr(),
+                  oi.data_ptr(), _ext.stream_ptr(xs.device))
     return ov.item(), int(oi.item())
 
 
 def max_element(x: torch.Tensor) -> tuple[float, int]:
-    """(max value, first index of it)."""
+    """(max value, first index of it) of float32 / int32 / int64 / float64
+    data. NaN never wins: NaNs are skipped, the result is the first index of
+    the maximum of the other elements (-0.0 == 0.0: the first of them); an
+    all-NaN input gives ``(nan, 0)``."""
     return _arg(x, True)
 
 
 def min_element(x: torch.Tensor) -> tuple[float, int]:
-    """(min value, first index of it)."""
+    """(min value, first index of it); NaNs are skipped as in
+    :func:`max_element`, an all-NaN input gives ``(nan, 0)``."""
     return _arg(x, False)
 
 
@@ -287,9 +314,9 @@ def inner_product(a: torch.Tensor, b: torch.Tensor, op: str = "mul") -> float:
     if a.shape != b.shape:
         raise ValueError("shape mismatch")
     if a.element_size() != 4:
-        raise TypeError("32-bit elements expected")
+        raise TypeError(f"inner_product: 32-bit elements expected, got {a.dtype}")
     if op == "mul" and a.dtype != torch.float32:
-        raise TypeError("op='mul' takes float32")
+        raise TypeError(f"inner_product: op='mul' takes float32, got {a.dtype}")
     aa, bb = a.contiguous().view(-1), b.contiguous().view(-1)
     if not a.is_cuda:
         out = ctypes.c_double(0.0)
@@ -304,6 +331,10 @@ def inner_product(a: torch.Tensor, b: torch.Tensor, op: str = "mul") -> float:
 
 
 # ------------------------------------------------------------------ oracles
+# Numeric semantics (torch's ==): ref_unique / ref_run_starts / ref_remove_value
+# merge -0.0 with 0.0 and keep every NaN apart, where the backends compare bit
+# patterns; ref_arg does not skip NaN. tests/test_algorithms_edges.py has the
+# bit-pattern oracles.
 def _ref_mask(x: torch.Tensor, flags, pred: str, value, invert: bool) -> torch.Tensor:
     x = x.reshape(-1)
     if pred == "flags":

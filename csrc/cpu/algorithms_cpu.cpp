@@ -107,7 +107,17 @@ void seg_reduce_t(const void* vals, const int64_t* off, long long nseg, int op, 
     }
 }
 
-// first index of the max (min); NaN never wins a comparison
+template <typename T>
+inline bool is_nan(T x) {
+    if constexpr (std::numeric_limits<T>::has_quiet_NaN)
+        return x != x;
+    else
+        return false;
+}
+
+// first index of the max (min). NaN never wins: NaNs are skipped wherever
+// they sit, so the result is the extremum of the other elements; all NaN:
+// (NaN, 0)
 template <typename T>
 void arg_reduce_t(const void* x, long long n, bool is_max, void* val, int64_t* idx) {
     const T* v = (const T*)x;
@@ -119,20 +129,25 @@ void arg_reduce_t(const void* x, long long n, bool is_max, void* val, int64_t* i
         const int t = omp_get_thread_num(), tn = omp_get_num_threads();
         long long b, e;
         share(n, t, tn, &b, &e);
-        if (b < e) {
-            T best = v[b];
-            long long bidx = b;
-            for (long long i = b + 1; i < e; ++i)
-                if (is_max ? v[i] > best : v[i] < best) best = v[i], bidx = i;
-            bv[t] = best;
-            bi[t] = bidx;
+        T best{};
+        long long bidx = -1;
+        for (long long i = b; i < e; ++i) {
+            const T c = v[i];
+            if (is_nan(c)) continue;
+            if (bidx < 0 || (is_max ? c > best : c < best)) best = c, bidx = i;
         }
+        bv[t] = best;
+        bi[t] = bidx;
     }
     T best{};
     long long bidx = -1;
     for (int t = 0; t < nt; ++t) {  // threads hold increasing index ranges: strict compare keeps the first
         if (bi[t] < 0) continue;
         if (bidx < 0 || (is_max ? bv[t] > best : bv[t] < best)) best = bv[t], bidx = bi[t];
+    }
+    if (bidx < 0) {  // n > 0 and nothing but NaN
+        best = std::numeric_limits<T>::quiet_NaN();
+        bidx = 0;
     }
     memcpy(val, &best, sizeof(T));
     *idx = bidx;

@@ -20,7 +20,8 @@
 //                the top levels of every search share cache lines in L2).
 //  seg_reduce  : reduce_by_key values given segment offsets, one wave per
 //                segment (DPP wave reduction), sum / max / min.
-//  arg_reduce  : max_element / min_element (first index on ties), two-pass.
+//  arg_reduce  : max_element / min_element (first index on ties; NaNs are
+//                skipped), two-pass.
 //  inner       : inner_product with (plus, multiplies) in fp32 with a fp64
 //                per-lane accumulator, or (plus, equal_to) counting matches.
 #include "cme213/common.h"
@@ -365,10 +366,22 @@ struct ArgPair {
     long long i;
 };
 
+template <typename T>
+__device__ __forceinline__ bool arg_is_nan(T x) {
+    if constexpr (std::is_floating_point<T>::value)
+        return x != x;
+    else
+        return false;
+}
+
+// Fold the candidate (v2, i2) into (v, i); i < 0 marks an empty side. NaN
+// never wins: a NaN candidate is dropped like an empty one, so no accumulator
+// ever holds a NaN and both partner lanes of the butterfly in block_arg
+// compute the same pair. All-NaN input leaves i < 0 (arg_final_kernel).
 template <typename T, bool MAX>
 __device__ __forceinline__ void arg_combine(T& v, long long& i, T v2, long long i2) {
     const bool better = MAX ? (v2 > v || (v2 == v && i2 < i)) : (v2 < v || (v2 == v && i2 < i));
-    if (i < 0 || (i2 >= 0 && better)) {
+    if (i2 >= 0 && !arg_is_nan(v2) && (i < 0 || better)) {
         v = v2;
         i = i2;
     }
@@ -429,6 +442,12 @@ __global__ __launch_bounds__(kThreads) void arg_final_kernel(const T* __restrict
     for (int k = threadIdx.x; k < np; k += kThreads) arg_combine<T, MAX>(v, idx, pv[k], pi[k]);
     block_arg<T, MAX>(v, idx, sv, si);
     if (threadIdx.x == 0) {
+        if constexpr (std::is_floating_point<T>::value) {
+            if (idx < 0) {  // nothing but NaN
+                v = (T)__builtin_nanf("");
+                idx = 0;
+            }
+        }
         *ov = v;
         *oi = idx;
     }
@@ -613,13 +632,14 @@ CME_EXPORT int cme_search(const void* sorted, long long n, const void* q, long l
     }
 }
 
-// dtype: 0 f32, 1 i32, 4 f64; op: 0 sum, 1 max, 2 min
+// dtype: 0 f32, 1 i32, 3 i64, 4 f64; op: 0 sum, 1 max, 2 min
 CME_EXPORT int cme_seg_reduce(const void* v, const long long* offsets, long long nseg, int dtype, int op, void* out,
                               void* stream) {
     hipStream_t s = as_stream(stream);
     switch (dtype) {
         case 0: return seg_reduce_impl<float>((const float*)v, offsets, nseg, op, (float*)out, s);
         case 1: return seg_reduce_impl<int>((const int*)v, offsets, nseg, op, (int*)out, s);
+        case 3: return seg_reduce_impl<long long>((const long long*)v, offsets, nseg, op, (long long*)out, s);
         case 4: return seg_reduce_impl<double>((const double*)v, offsets, nseg, op, (double*)out, s);
         default: return (int)hipErrorInvalidValue;
     }
@@ -627,7 +647,8 @@ CME_EXPORT int cme_seg_reduce(const void* v, const long long* offsets, long long
 
 CME_EXPORT long long cme_arg_ws_bytes() { return 16LL * kArgBlocks; }
 
-// max_element / min_element: dtype 0 f32, 1 i32, 4 f64; is_max 1/0.
+// max_element / min_element: dtype 0 f32, 1 i32, 3 i64, 4 f64; is_max 1/0.
+// NaNs are skipped; all NaN: (NaN, 0).
 CME_EXPORT int cme_arg_reduce(const void* x, long long n, int dtype, int is_max, void* ws, void* out_val,
                               long long* out_idx, void* stream) {
     hipStream_t s = as_stream(stream);
@@ -638,6 +659,7 @@ CME_EXPORT int cme_arg_reduce(const void* x, long long n, int dtype, int is_max,
     switch (dtype) {
         case 0: CME_ARG(float);
         case 1: CME_ARG(int);
+        case 3: CME_ARG(long long);
         case 4: CME_ARG(double);
         default: return (int)hipErrorInvalidValue;
     }
