@@ -14,7 +14,9 @@
 // wide-lane pipelined pass the reassociated form with its terms interleaved
 // across a lane's 8 points (heat_pipe.h FMA arm 5) runs 6.5 % faster than the
 // FMA-contracted pass on random data at 16384^2 and 8 % faster on one N = 8
-// rank's 2048-row share (profiles/heat_fast_r4.md).
+// rank's 2048-row share (profiles/heat_fast_r4.md). The pass launched here is
+// arm 6: the same operations written on explicit float pairs, 83-86 instead of
+// 90-97 VALU instructions per row update (profiles/heat_isa_census_r7.md).
 //
 // Entry points:
 //   cme_heat_step_fast_f32/f64 : one step over a region (a plain one-thread-
@@ -83,8 +85,9 @@ CME_EXPORT int cme_heat_step_fast_f64(const double* prev, double* curr, int pitc
 }
 
 // nsteps (2-4) reassociated timesteps in one pass of the wide-lane pipelined
-// kernel (fp32, order 8: FMA arm 5 = terms interleaved across the lane's 8
-// points, registers capped for 3 waves per SIMD), like cme_heat_pipe_f32:
+// kernel (fp32, order 8: FMA arm 6 = terms interleaved across the lane's 8
+// points on explicit float pairs, role 0 loading straight into its window,
+// registers capped for 3 waves per SIMD), like cme_heat_pipe_f32:
 // intermediate steps over `ext`, the last writes the nout (<= 4) regions of
 // `out`. flag != nullptr: regions [wait_from, nout) wait for *flag >= value
 // first (the fused distributed schedule; timeout: the sticky give-up word).
@@ -110,10 +113,11 @@ CME_EXPORT int cme_heat_pipe_fast_f32(const float* prev, float* curr, int pitch,
     // (168 VGPRs, 32 B/lane of scratch) -- 0.1537 vs 0.1653 ms/step uncapped
     // (2 waves per SIMD) on random data; two / three steps (remainders only)
     // uncapped: the same cap spills hundreds of bytes per lane there
+    // (measured on arm 5; arm 6 needs 138 VGPRs at any of the three)
     switch (nsteps) {
-        case 2: return launch_pipe_multi<float, 8, 2, 5, 2, 1, true, 1, 8>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
-        case 3: return launch_pipe_multi<float, 8, 3, 5, 2, 1, true, 1, 8>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
-        case 4: return launch_pipe_multi<float, 8, 4, 5, 2, 1, true, 1, 8, 3>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
+        case 2: return launch_pipe_multi<float, 8, 2, 6, 2, 1, true, 1, 8>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
+        case 3: return launch_pipe_multi<float, 8, 3, 6, 2, 1, true, 1, 8>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
+        case 4: return launch_pipe_multi<float, 8, 4, 6, 2, 1, true, 1, 8, 3>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
         default: return (int)hipErrorInvalidValue;
     }
 }
@@ -144,5 +148,5 @@ CME_EXPORT int cme_heat_run_fast_f32(float* a, float* b, int pitch, int gy, int 
 }
 
 // kernels in the occupancy / resource report (cme_kernel_query)
-CME_REGISTER_KERNEL(heat_pipe4w_fast_f32_o8, 256, heat_pipe_kernel<float, 8, 2, 4, 5, 1, true, 1, 8, 3>);
+CME_REGISTER_KERNEL(heat_pipe4w_fast_f32_o8, 256, heat_pipe_kernel<float, 8, 2, 4, 6, 1, true, 1, 8, 3>);
 CME_REGISTER_KERNEL(heat_step_fast_f32_o8, 256, heat_step_fast_kernel<float, 8>);

@@ -63,6 +63,10 @@ __device__ __forceinline__ float uniform_f(float v) {
 // 8-column boundaries so no lane straddles the grid edge (profiles/
 // heat_pipe_wide_r3.md). FMA = 4 issues the FMA chains of the lane's points
 // term by term (heat_d2_fma_n): the same operations per point, interleaved.
+// FMA = 6 (the fast production pass) writes the reassociated update on
+// explicit float pairs (upd_packed) and lets role 0 load into its window
+// directly: 83-86 VALU instructions per row update instead of 90-97 for the
+// same 68 arithmetic ones (profiles/heat_isa_census_r7.md).
 //
 // LX (x-neighbours from LDS): roles 1..NS-1 read the B edge columns of the
 // lanes on either side of their centre rows back from the ring (two 16-B LDS
@@ -86,16 +90,28 @@ struct PipeN {
     // FMA: 0 exact, 1 FMA-contracted (the reference's nvcc -fmad code), 2 / 3
     // reassociated ("fast"; 3 capped at 4 waves/SIMD), 4 FMA-contracted with
     // the chains of the lane's VW points interleaved term by term (bitwise 1),
-    // 5 reassociated with the terms interleaved across the points (bitwise 2)
-    static constexpr bool kFast = FMA == 2 || FMA == 3 || FMA == 5;
+    // 5 reassociated with the terms interleaved across the points (bitwise 2),
+    // 6 the same operations on explicit float pairs (wide lanes; bitwise 2):
+    // see upd_packed
+    static constexpr bool kPacked = FMA == 6;
+    static constexpr bool kFast = FMA == 2 || FMA == 3 || FMA == 5 || kPacked;
     static constexpr bool kTermMajor = FMA == 4;
     static constexpr bool kFastTM = FMA == 5;  // reassociated, terms issued across the lane's points
+    static_assert(!kPacked || (VW == 8 && sizeof(T) == 4 && ORDER == 8 && WPR == 1 && !LX),
+                  "pipe: the packed-pair update is fp32, order 8, wide lanes, DPP x-neighbours");
+    // kPacked: role 0 loads every input row straight into the window slot it
+    // is read from -- PD*RB more slots, the rows in flight, instead of `nxt`
+    // and a register copy per loaded row -- so its phases unroll over Q0
+    // (NW0 / gcd(NW0, RB): 6 at RB = 2, PD = 1) instead of Q. Roles 1.. keep
+    // the NW-slot window.
+    static constexpr int NW0 = kPacked ? NW + PD * RB : NW;
+    static constexpr int Q0 = kPacked ? NW0 / cgcd(NW0, RB) : Q;
     using VT = VecN<T, VW>;
     using Ring = V4<T>[NSLOT][RB][NH][LW];
     using Edge = V4<T>[3][RB][WPR][2];
 
-    VT w[NW];           // window of step-k rows (k = this wave's role); slot j = row r0 - (k+1)B + j
-    VT nxt[PD][RB];     // role 0: input rows of the next PD phases, in flight
+    VT w[NW0];          // window of step-k rows (k = this wave's role); slot j = row r0 - (k+1)B + j
+    VT nxt[PD][RB];     // role 0: input rows of the next PD phases, in flight (!kPacked)
     Ring* ring;         // ring[k]: step-(k+1) rows from role k to role k+1
     Edge* edge;         // edge[k]: seam lanes of the step-k rows role k received (WPR > 1)
     const T* src;
@@ -126,9 +142,80 @@ struct PipeN {
     // seam of WPR > 1 takes the neighbour wave's value from `ev`). VW = 8
     // moves 2B = 8 values per 8 points instead of per 4, and pairs more of the
     // x operands inside one lane for the packed FMAs.
-    template <bool MASK, bool FROM_LDS = false>
+    // kPacked: one output row of 8 columns on explicit float pairs. The row
+    // r[0..16) (4 halo + 8 own + 4 halo columns) is held as its 8 aligned
+    // pairs E[m] = (r[2m], r[2m+1]) -- the own pairs are the window's
+    // registers, the DPP moves write the halo pair elements directly -- and
+    // its 7 odd pairs O[m] = (r[2m+1], r[2m+2]), one shuffle (v_pk_mov_b32)
+    // each: every x operand of the column pairs (0,1) (2,3) (4,5) (6,7) is
+    // then one of these 15 register pairs. Per point the operations and their
+    // order are heat_update_fast's (c0 c, the x pairs, the y pairs,
+    // k = B-1..0), each term issued across the four column pairs first:
+    // 4 v_pk_mul_f32 + 32 v_pk_add_f32 + 32 v_pk_fma_f32 + 8 DPP moves + 7
+    // pair moves per row. WN: slots of this role's window.
+    template <bool MASK, int WN>
+    __device__ __forceinline__ VT upd_packed(int s_lo, int row) const {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+        typedef float f2 __attribute__((ext_vector_type(2)));
+        constexpr int NP = VW / 2;  // column pairs per lane
+        const VT& c = w[(s_lo + B) % WN];
+        f2 E[NP + B], O[NP + B - 1];
+#pragma unroll
+        for (int m = 0; m < B / 2; ++m) {
+            E[m] = f2{dpp_shift<kDppWaveShr1>(c[VW - B + 2 * m]), dpp_shift<kDppWaveShr1>(c[VW - B + 2 * m + 1])};
+            E[B / 2 + NP + m] = f2{dpp_shift<kDppWaveShl1>(c[2 * m]), dpp_shift<kDppWaveShl1>(c[2 * m + 1])};
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p) E[B / 2 + p] = f2{c[2 * p], c[2 * p + 1]};
+#pragma unroll
+        for (int m = 0; m < NP + B - 1; ++m) O[m] = __builtin_shufflevector(E[m], E[m + 1], 1, 2);
+        // the pair (r[i], r[i+1])
+        auto rp = [&](int i) { return (i & 1) ? O[i >> 1] : E[i >> 1]; };
+        f2 u[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) u[p] = f2(fc.c0) * E[B / 2 + p];
+#pragma unroll
+        for (int k = B - 1; k >= 0; --k)
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+                u[p] = __builtin_elementwise_fma(f2(fc.ax[k]), rp(B + 2 * p + (k + 1)) + rp(B + 2 * p - (k + 1)), u[p]);
+#pragma unroll
+        for (int k = B - 1; k >= 0; --k) {
+            const VT& yp = w[(s_lo + B + (k + 1)) % WN];
+            const VT& ym = w[(s_lo + B - (k + 1)) % WN];
+            // the four pair sums of a term before its four FMAs (no VALU
+            // crosses the barrier): left alone the scheduler ends the row
+            // with add, FMA, add, FMA on one temporary pair, and every FMA
+            // reading the sum written just before it costs an s_nop (7 per
+            // row, profiles/heat_isa_census_r7.md)
+            f2 a[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) a[p] = f2{yp[2 * p], yp[2 * p + 1]} + f2{ym[2 * p], ym[2 * p + 1]};
+            __builtin_amdgcn_sched_barrier(0x94);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) u[p] = __builtin_elementwise_fma(f2(fc.ay[k]), a[p], u[p]);
+        }
+        bool row_in = true;
+        if constexpr (MASK) row_in = row >= yb1 && row < ye1;
+        VT o;
+#pragma unroll
+        for (int j = 0; j < VW; ++j) {
+            if constexpr (MASK) {
+                const int x = xbase + j;
+                o[j] = (row_in && x >= xb1 && x < xe1) ? u[j / 2][j % 2] : c[j];
+            } else {
+                o[j] = u[j / 2][j % 2];
+            }
+        }
+        return o;
+    }
+
+    template <bool MASK, bool FROM_LDS = false, int WN = NW>
     __device__ __forceinline__ VT upd(int s_lo, int row, const V4<T>& ev, const V4<T>& xl = V4<T>{},
                                       const V4<T>& xr = V4<T>{}) const {
+        if constexpr (kPacked) return upd_packed<MASK, WN>(s_lo, row);
         const VT c = w[(s_lo + B) % NW];
         T rowv[VW + 2 * B];
         if constexpr (FROM_LDS) {  // the left lane's last B columns, the right lane's first B
@@ -278,14 +365,22 @@ struct PipeN {
     template <int K, int PH>
     __device__ __forceinline__ bool phase() {
         if (r0 - (NS - 1) * B >= y1) return false;
-        constexpr int S = (PH * RB) % NW;
+        constexpr int WN = K == 0 ? NW0 : NW;  // slots of this role's window
+        constexpr int QK = K == 0 ? Q0 : Q;    // its unroll period
+        constexpr int S = (PH * RB) % WN;
         constexpr int ST = K + 1;  // the timestep this role computes
         const int par = q % NSLOT;
         const int cslot = (q + NSLOT - B / RB) % NSLOT;  // LX: slot of this phase's centre rows
-        if constexpr (K == 0) {
+        if constexpr (K == 0 && kPacked) {
+            // the rows PD phases ahead, into the slots of the rows this phase
+            // no longer reads; unconditional for the reason given below
+#pragma unroll
+            for (int i = 0; i < RB; ++i)
+                w[(S + 2 * B + PD * RB + i) % WN] = load_n<VW>(row_ptr(r0 + PD * RB + B + i));
+        } else if constexpr (K == 0) {
             constexpr int F = PH % PD;
 #pragma unroll
-            for (int i = 0; i < RB; ++i) w[(S + 2 * B + i) % NW] = nxt[F][i];
+            for (int i = 0; i < RB; ++i) w[(S + 2 * B + i) % WN] = nxt[F][i];
             // unconditional (row_ptr clamps to the grid): a guarded prefetch
             // becomes a phi whose register copies wait on the loads just issued
 #pragma unroll
@@ -297,7 +392,7 @@ struct PipeN {
                 for (int h = 0; h < NH; ++h) {
                     const V4<T> v = ring[K - 1][par][i][h][glane];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) w[(S + 2 * B + i) % NW][4 * h + j] = v[j];
+                    for (int j = 0; j < 4; ++j) w[(S + 2 * B + i) % WN][4 * h + j] = v[j];
                 }
         }
         V4<T> ev[RB];
@@ -311,7 +406,7 @@ struct PipeN {
             if (lane == 0 || lane == 63) {
 #pragma unroll
                 for (int i = 0; i < RB; ++i)
-                    edge[K][e3][i][sub][lane == 63 ? 1 : 0] = piece4(w[(S + 2 * B + i) % NW], 0);
+                    edge[K][e3][i][sub][lane == 63 ? 1 : 0] = piece4(w[(S + 2 * B + i) % WN], 0);
             }
         }
 #pragma unroll
@@ -321,20 +416,20 @@ struct PipeN {
                 if (row >= y0 - (NS - ST) * B && row < y1 + (NS - ST) * B) {
                     VT o;
                     if constexpr (LX && K > 0)
-                        o = upd<CHECK, true>((S + i) % NW, row, ev[i], ring[K - 1][cslot][i][NH - 1][gl_l],
+                        o = upd<CHECK, true>((S + i) % WN, row, ev[i], ring[K - 1][cslot][i][NH - 1][gl_l],
                                              ring[K - 1][cslot][i][0][gl_r]);
                     else
-                        o = upd<CHECK>((S + i) % NW, row, ev[i]);
+                        o = upd<CHECK, false, WN>((S + i) % WN, row, ev[i]);
 #pragma unroll
                     for (int h = 0; h < NH; ++h) ring[K][par][i][h][glane] = piece4(o, h);
                 }
             } else if (row >= y0 && row < y1) {
                 VT o;
                 if constexpr (LX && K > 0)
-                    o = upd<false, true>((S + i) % NW, row, ev[i], ring[K - 1][cslot][i][NH - 1][gl_l],
+                    o = upd<false, true>((S + i) % WN, row, ev[i], ring[K - 1][cslot][i][NH - 1][gl_l],
                                          ring[K - 1][cslot][i][0][gl_r]);
                 else
-                    o = upd<false>((S + i) % NW, row, ev[i]);
+                    o = upd<false, false, WN>((S + i) % WN, row, ev[i]);
                 T* d = dst + (size_t)row * pitch;
                 bool wt = false;
                 if constexpr (OST != 0) wt = OST == 1 || row < wt_lo || row >= wt_hi;
@@ -367,7 +462,7 @@ struct PipeN {
         ++q;
         if constexpr (WPR > 1) e3 = e3 == 2 ? 0 : e3 + 1;
         __syncthreads();
-        if constexpr (PH + 1 < Q)
+        if constexpr (PH + 1 < QK)
             return phase<K, PH + 1>();
         else
             return true;
@@ -386,7 +481,13 @@ struct PipeN {
 #pragma unroll
             for (int f = 0; f < PD; ++f)
 #pragma unroll
-                for (int i = 0; i < RB; ++i) nxt[f][i] = load_n<VW>(row_ptr(r0 + f * RB + B + i));
+                for (int i = 0; i < RB; ++i) {
+                    const VT v = load_n<VW>(row_ptr(r0 + f * RB + B + i));
+                    if constexpr (kPacked)
+                        w[2 * B + f * RB + i] = v;
+                    else
+                        nxt[f][i] = v;
+                }
             if constexpr (WPR > 1) {  // seams of the first phase's centre rows (window slots B..2B-1)
                 if (lane == 0 || lane == 63) {
 #pragma unroll
@@ -451,7 +552,7 @@ __device__ __forceinline__ void pipen_run(V4<T> (*ring)[NSLOT][RB][VW / 4][64 * 
     st.ye1 = ye1;
     st.xcfl = xcfl;
     st.ycfl = ycfl;
-    if constexpr (FMA == 2 || FMA == 3 || FMA == 5) {
+    if constexpr (decltype(st)::kFast) {
         const HeatFast<ORDER, T> f = heat_fast_coefs<ORDER>(xcfl, ycfl);
         st.fc.c0 = uniform_f(f.c0);
 #pragma unroll
