@@ -47,7 +47,7 @@ def _hip_flags() -> list[str]:
     opt = ["-O1", "-g"] if _debug() else ["-O3"]
     return opt + [
         f"--offload-arch={ARCH}",
-        "-std=c++17",
+        "-std=c++20",
         "-fPIC",
         "-munsafe-fp-atomics",
         "-Wall",

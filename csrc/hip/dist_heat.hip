@@ -403,7 +403,7 @@ int launch_wait(const FlagList& l, unsigned v, unsigned* timeout, hipStream_t s)
 }
 
 // bit 3 of the flags word: reassociated ("fast") arithmetic, fp32 order 8
-// (heat_fast.hip: the wide-lane pipelined pass with FMA arm 5 for 2-4 step
+// (heat_fast.hip: the wide-lane pipelined pass, kFastPacked, for 2-4 step
 // passes, a plain kernel for single steps)
 constexpr int kArithFast = 8;
 

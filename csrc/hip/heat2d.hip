@@ -141,8 +141,7 @@ CME_EXPORT int cme_heat_step2_f32(const float* prev, float* curr, int pitch, int
                                   const int* ext, int order, float xcfl, float ycfl, int chunk, int fma,
                                   void* stream) {
     Region gs[kMaxS2Regions];
-    if (nout < 1 || nout > kMaxS2Regions) return (int)hipErrorInvalidValue;
-    for (int i = 0; i < nout; ++i) gs[i] = Region{out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]};
+    if (!regions_from(out, nout, gs)) return (int)hipErrorInvalidValue;
     return dispatch_stream2<float>(order, prev, curr, pitch, gy, gs, nout, Region{ext[0], ext[1], ext[2], ext[3]},
                                    xcfl, ycfl, chunk, fma, as_stream(stream));
 }
@@ -151,8 +150,7 @@ CME_EXPORT int cme_heat_step2_f64(const double* prev, double* curr, int pitch, i
                                   const int* ext, int order, double xcfl, double ycfl, int chunk, int fma,
                                   void* stream) {
     Region gs[kMaxS2Regions];
-    if (nout < 1 || nout > kMaxS2Regions) return (int)hipErrorInvalidValue;
-    for (int i = 0; i < nout; ++i) gs[i] = Region{out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]};
+    if (!regions_from(out, nout, gs)) return (int)hipErrorInvalidValue;
     return dispatch_stream2<double>(order, prev, curr, pitch, gy, gs, nout, Region{ext[0], ext[1], ext[2], ext[3]},
                                     xcfl, ycfl, chunk, fma, as_stream(stream));
 }
@@ -189,8 +187,7 @@ CME_EXPORT int cme_heat_stepn_f32(const float* prev, float* curr, int pitch, int
                                   const int* ext, int order, int nsteps, float xcfl, float ycfl, int chunk, int fma,
                                   void* stream) {
     Region gs[kMaxS2Regions];
-    if (nout < 1 || nout > kMaxS2Regions) return (int)hipErrorInvalidValue;
-    for (int i = 0; i < nout; ++i) gs[i] = Region{out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]};
+    if (!regions_from(out, nout, gs)) return (int)hipErrorInvalidValue;
     const Region e{ext[0], ext[1], ext[2], ext[3]};
     return fma ? stepn_f32_o<true>(order, prev, curr, pitch, gy, gs, nout, e, nsteps, xcfl, ycfl, chunk,
                                    as_stream(stream))
@@ -225,8 +222,7 @@ CME_EXPORT int cme_heat_stepn_f64(const double* prev, double* curr, int pitch, i
         return cme_heat_step2_f64(prev, curr, pitch, gy, out, nout, ext, order, xcfl, ycfl, chunk, fma, stream);
     if (nsteps != 3) return (int)hipErrorInvalidValue;  // 4-step passes: fp32 only
     Region gs[kMaxS2Regions];
-    if (nout < 1 || nout > kMaxS2Regions) return (int)hipErrorInvalidValue;
-    for (int i = 0; i < nout; ++i) gs[i] = Region{out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]};
+    if (!regions_from(out, nout, gs)) return (int)hipErrorInvalidValue;
     const Region e{ext[0], ext[1], ext[2], ext[3]};
     return fma ? stepn3_f64_o<true>(order, prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, as_stream(stream))
                : stepn3_f64_o<false>(order, prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, as_stream(stream));

@@ -12,11 +12,12 @@
 //
 // Why it exists: the flagship pass is VALU-issue and power bound. On the
 // wide-lane pipelined pass the reassociated form with its terms interleaved
-// across a lane's 8 points (heat_pipe.h FMA arm 5) runs 6.5 % faster than the
-// FMA-contracted pass on random data at 16384^2 and 8 % faster on one N = 8
-// rank's 2048-row share (profiles/heat_fast_r4.md). The pass launched here is
-// arm 6: the same operations written on explicit float pairs, 83-86 instead of
-// 90-97 VALU instructions per row update (profiles/heat_isa_census_r7.md).
+// across a lane's 8 points (heat_pipe.h kFastTermMajor) runs 6.5 % faster than
+// the FMA-contracted pass on random data at 16384^2 and 8 % faster on one
+// N = 8 rank's 2048-row share (profiles/heat_fast_r4.md). The pass launched
+// here is kFastPacked: the same operations written on explicit float pairs,
+// 83-86 instead of 90-97 VALU instructions per row update (profiles/
+// heat_isa_census_r7.md).
 //
 // Entry points:
 //   cme_heat_step_fast_f32/f64 : one step over a region (a plain one-thread-
@@ -84,40 +85,35 @@ CME_EXPORT int cme_heat_step_fast_f64(const double* prev, double* curr, int pitc
     return step_fast<double>(prev, curr, pitch, Region{xb, xe, yb, ye}, order, xcfl, ycfl, as_stream(stream));
 }
 
-// nsteps (2-4) reassociated timesteps in one pass of the wide-lane pipelined
-// kernel (fp32, order 8: FMA arm 6 = terms interleaved across the lane's 8
-// points on explicit float pairs, role 0 loading straight into its window,
-// registers capped for 3 waves per SIMD), like cme_heat_pipe_f32:
-// intermediate steps over `ext`, the last writes the nout (<= 4) regions of
-// `out`. flag != nullptr: regions [wait_from, nout) wait for *flag >= value
-// first (the fused distributed schedule; timeout: the sticky give-up word).
+// The wide-lane pipelined pass of the reassociated arithmetic (fp32, order 8:
+// kFastPacked = terms interleaved across the lane's 8 points on explicit
+// float pairs, role 0 loading straight into its window).
+// Four steps (the production pass): registers capped for 3 waves per SIMD
+// (168 VGPRs, 32 B/lane of scratch) -- 0.1537 vs 0.1653 ms/step uncapped
+// (2 waves per SIMD) on random data; two / three steps (remainders only)
+// uncapped: the same cap spills hundreds of bytes per lane there
+// (measured on kFastTermMajor; kFastPacked needs 138 VGPRs at any of the three)
+constexpr PipeCfg kFastPassRem{.arith = kFastPacked, .rb = 2, .nt = true, .vw = 8};
+constexpr PipeCfg kFastPass4{.ns = 4, .arith = kFastPacked, .rb = 2, .nt = true, .vw = 8, .occ = 3};
+
+// nsteps (2-4) reassociated timesteps in one pass of that kernel, like
+// cme_heat_pipe_f32: intermediate steps over `ext`, the last writes the nout
+// (<= 4) regions of `out`. flag != nullptr: regions [wait_from, nout) wait
+// for *flag >= value first (the fused distributed schedule; timeout: the
+// sticky give-up word).
 CME_EXPORT int cme_heat_pipe_fast_f32(const float* prev, float* curr, int pitch, int gy, const int* out, int nout,
                                       const int* ext, int order, int nsteps, float xcfl, float ycfl, int chunk,
                                       int wait_from, const unsigned* flag, unsigned value, unsigned* timeout,
                                       void* stream) {
     Region gs[kMaxS2Regions];
-    if (order != 8 || nout < 1 || nout > kMaxS2Regions || (flag && !timeout)) return (int)hipErrorInvalidValue;
-    for (int i = 0; i < nout; ++i) gs[i] = Region{out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]};
+    if (order != 8 || !regions_from(out, nout, gs) || (flag && !timeout)) return (int)hipErrorInvalidValue;
     const Region e{ext[0], ext[1], ext[2], ext[3]};
-    PipeGate gate;
-    if (flag) {
-        gate.flag = flag;
-        gate.val = value;
-        gate.from = wait_from;
-        gate.timeout = timeout;
-        const long v = cme::tune_get(cme::kTuneDistGateSpins);
-        gate.spins = v > 0 ? (unsigned)v : (1u << 24);
-    }
+    const PipeGate gate = make_gate(flag, value, wait_from, timeout);
     hipStream_t s = as_stream(stream);
-    // four steps (the production pass): registers capped for 3 waves per SIMD
-    // (168 VGPRs, 32 B/lane of scratch) -- 0.1537 vs 0.1653 ms/step uncapped
-    // (2 waves per SIMD) on random data; two / three steps (remainders only)
-    // uncapped: the same cap spills hundreds of bytes per lane there
-    // (measured on arm 5; arm 6 needs 138 VGPRs at any of the three)
     switch (nsteps) {
-        case 2: return launch_pipe_multi<float, 8, 2, 6, 2, 1, true, 1, 8>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
-        case 3: return launch_pipe_multi<float, 8, 3, 6, 2, 1, true, 1, 8>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
-        case 4: return launch_pipe_multi<float, 8, 4, 6, 2, 1, true, 1, 8, 3>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
+        case 2: return launch_pipe_multi<float, with(kFastPassRem, 2)>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
+        case 3: return launch_pipe_multi<float, with(kFastPassRem, 3)>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
+        case 4: return launch_pipe_multi<float, kFastPass4>(prev, curr, pitch, gy, gs, nout, e, xcfl, ycfl, chunk, 0, s, gate);
         default: return (int)hipErrorInvalidValue;
     }
 }
@@ -148,5 +144,5 @@ CME_EXPORT int cme_heat_run_fast_f32(float* a, float* b, int pitch, int gy, int 
 }
 
 // kernels in the occupancy / resource report (cme_kernel_query)
-CME_REGISTER_KERNEL(heat_pipe4w_fast_f32_o8, 256, heat_pipe_kernel<float, 8, 2, 4, 6, 1, true, 1, 8, 3>);
+CME_REGISTER_KERNEL(heat_pipe4w_fast_f32_o8, 256, heat_pipe_kernel<float, kFastPass4>);
 CME_REGISTER_KERNEL(heat_step_fast_f32_o8, 256, heat_step_fast_kernel<float, 8>);

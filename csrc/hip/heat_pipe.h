@@ -7,13 +7,17 @@
 // timesteps of one strip-chunk split across the waves of a workgroup.
 //
 // Kernel template, chunk rule and launcher; the C entry points are in
-// heat_pipe.hip (production) and heat_pipe_tune.hip (tuning arms).
+// heat_pipe.hip (production) and heat_pipe_tune.hip (tuning arms). A kernel
+// is named by its element type and one PipeCfg value (cme213/
+// heat_pipe_cfg.h); the text below calls the axes by PipeCfg's field names,
+// and PipeN spells them NS = ns, RB = rb, ... in its arithmetic.
 #pragma once
 #include <limits.h>
 #include <stdlib.h>
 
 #include "cme213/common.h"
 #include "cme213/tuning.h"
+#include "cme213/heat_pipe_cfg.h"
 #include "cme213/heat_region.h"
 #include "cme213/heat_stencil.h"
 #include "cme213/vec.h"
@@ -26,56 +30,73 @@ __device__ __forceinline__ float uniform_f(float v) {
 }
 
 // ---------------------------------------------------------------- pipe
-// Wave-pipelined temporal blocking: NS (2..6) timesteps per HBM pass with the
+// Wave-pipelined temporal blocking: ns (2..6) timesteps per HBM pass with the
 // steps split ACROSS the waves of a workgroup instead of stacked in one wave.
+// B = order / 2 is the stencil's reach.
 //
-// A streamN wave keeps all NS step windows in its own VGPRs (210 at NS = 3:
-// two waves per SIMD) and re-computes 2(NS-1)B warm-up rows at the top of its
+// A streamN wave keeps all ns step windows in its own VGPRs (210 at ns = 3:
+// two waves per SIMD) and re-computes 2(ns-1)B warm-up rows at the top of its
 // chunk -- a fixed cost per wave that grows to a third of the pass when a
 // strong-scaled subdomain hands every wave a short chunk (profiles/
-// dist_rank_r2.md). Here a workgroup of NS waves shares ONE strip-chunk: wave
+// dist_rank_r2.md). Here a workgroup of ns waves shares ONE strip-chunk: wave
 // k holds only the window of step-k rows (k = 0: input), computes step k+1 on
-// lanes k+1..62-k and hands every block of RB rows to wave k+1 through a
+// lanes k+1..62-k and hands every block of rb rows to wave k+1 through a
 // double-buffered LDS ring (16 B per lane, conflict-free); wave 0 streams the
-// input from HBM with PD phases of loads in flight, wave NS-1 stores the
-// result. One workgroup barrier per phase orders the hand-offs, wave k running
-// k phases behind wave 0. Each wave then needs one (RB+2B)-row window (~100
-// VGPRs), and for a given occupancy a workgroup's chunk is NS times taller
-// than a streamN wave's, so the warm-up share per pass drops NS-fold. The
-// arithmetic per cell, the region masks and hence the result are those of
-// StreamN / NS single steps, bit for bit.
+// input from HBM with pd phases of loads in flight, wave ns-1 stores the
+// result (nt: with non-temporal stores). One workgroup barrier per phase
+// orders the hand-offs, wave k running k phases behind wave 0. Each wave then
+// needs one (rb+2B)-row window (~100 VGPRs; occ caps the registers for that
+// many waves per SIMD), and for a given occupancy a workgroup's chunk is ns
+// times taller than a streamN wave's, so the warm-up share per pass drops
+// ns-fold. The arithmetic per cell, the region masks and hence the result are
+// those of StreamN / ns single steps, bit for bit.
 //
-// WPR > 1 (waves per role): a role is WPR waves side by side, so a strip is
-// 64*WPR lanes wide and the 2*NS lanes each strip loses to the shrinking
-// valid range are amortised over WPR times more output columns (12.5 % of the
-// lanes at NS = 4, WPR = 1; 6.25 % at WPR = 2). The x-neighbours across the
+// wpr > 1 (waves per role): a role is wpr waves side by side, so a strip is
+// 64*wpr lanes wide and the 2*ns lanes each strip loses to the shrinking
+// valid range are amortised over wpr times more output columns (12.5 % of the
+// lanes at ns = 4, wpr = 1; 6.25 % at wpr = 2). The x-neighbours across the
 // seam between two waves of a role come from the LDS edge buffer: every wave
 // publishes the edge lanes (0 and 63) of the rows it receives in phase q; they
-// are the centre rows of phase q+1 (needs RB == B), which the neighbour wave
+// are the centre rows of phase q+1 (needs rb == B), which the neighbour wave
 // reads back as the `old` operand of its DPP shifts (the lane with no DPP
 // source keeps it). Three edge buffers, one barrier per phase.
 //
-// VW = 8 (wide lanes, the order-8 fp32 production pass): each lane holds 8
+// vw = 8 (wide lanes, the order-8 fp32 production pass): each lane holds 8
 // consecutive columns, so the 2B DPP moves of the x-neighbours serve 8 points
 // instead of 4, more packed-FMA operand pairs lie inside one lane, and a strip
-// loses ceil(NS*B/8) lanes per side instead of NS (60 of 64 lanes write at
-// NS = 4). 156 VGPRs at RB = 2: three waves per SIMD. Strips start on
+// loses ceil(ns*B/8) lanes per side instead of ns (60 of 64 lanes write at
+// ns = 4). 156 VGPRs at rb = 2: three waves per SIMD. Strips start on
 // 8-column boundaries so no lane straddles the grid edge (profiles/
-// heat_pipe_wide_r3.md). FMA = 4 issues the FMA chains of the lane's points
-// term by term (heat_d2_fma_n): the same operations per point, interleaved.
-// FMA = 6 (the fast production pass) writes the reassociated update on
-// explicit float pairs (upd_packed) and lets role 0 load into its window
-// directly: 83-86 VALU instructions per row update instead of 90-97 for the
-// same 68 arithmetic ones (profiles/heat_isa_census_r7.md).
+// heat_pipe_wide_r3.md).
 //
-// LX (x-neighbours from LDS): roles 1..NS-1 read the B edge columns of the
+// arith (PipeArith): kExact, kFma and kFast compute a lane's points one after
+// the other. kFmaTermMajor issues the FMA chains of the lane's points term by
+// term (heat_d2_fma_n) and kFastTermMajor the reassociated update likewise:
+// the same operations per point, interleaved. kFastPacked (the fast
+// production pass) writes the reassociated update on explicit float pairs
+// (upd_packed) and lets role 0 load into its window directly: 83-86 VALU
+// instructions per row update instead of 90-97 for the same 68 arithmetic
+// ones (profiles/heat_isa_census_r7.md).
+//
+// lx (x-neighbours from LDS): roles 1..ns-1 read the B edge columns of the
 // lanes on either side of their centre rows back from the ring (two 16-B LDS
 // reads per row) instead of shifting them across lanes with 2B DPP moves on
-// the VALU; the centre rows arrived B/RB phases earlier, so the ring keeps
-// 2 + B/RB slots. Role 0 (rows from HBM) keeps the DPP shifts.
-template <typename T, int ORDER, int RB, int NS, int FMA, bool CHECK, int PD, bool NT, int WPR = 1, int VW = 4,
-          bool LX = false, int OST = 0>
+// the VALU; the centre rows arrived B/rb phases earlier, so the ring keeps
+// 2 + B/rb slots. Role 0 (rows from HBM) keeps the DPP shifts.
+//
+// ost = 1 / 2 (the dataflow launch's hand-off, heat_flow.hip): every output
+// row / the rows outside [wt_lo, wt_hi) are stored write-through (sc1 buffer
+// stores) from the uniform base `obase` at lane column `oxl`, so a completion
+// flag needs no L2 write-back fence behind them for a reader on another XCD
+// (cdna_hip_programming.md §6 Guideline 16, R1).
+
+// CHECK: the grid-edge instantiation (region masks on the intermediate steps,
+// per-column output stores); pipe_task picks it per task.
+template <typename T, PipeCfg C, bool CHECK>
 struct PipeN {
+    static constexpr int ORDER = C.order, NS = C.ns, RB = C.rb, PD = C.pd, WPR = C.wpr, VW = C.vw, OST = C.ost;
+    static constexpr bool NT = C.nt, LX = C.lx;
+    static_assert(NS >= 2 && NS <= 6, "pipe: 2..6 steps per pass");
     static constexpr int B = HeatOrder<ORDER>::B;
     static constexpr int NW = RB + 2 * B;
     static constexpr int P = NW / cgcd(NW, RB);
@@ -87,16 +108,11 @@ struct PipeN {
     static_assert(VW == 4 || (VW == 8 && sizeof(T) == 4 && B <= VW), "pipe: wide lanes are fp32, 8 columns");
     static_assert(!LX || (WPR == 1 && B % RB == 0), "pipe: LDS x-neighbours need one wave per role, RB | B");
     static constexpr int NSLOT = LX ? 2 + B / RB : 2;  // ring slots per role hand-off
-    // FMA: 0 exact, 1 FMA-contracted (the reference's nvcc -fmad code), 2 / 3
-    // reassociated ("fast"; 3 capped at 4 waves/SIMD), 4 FMA-contracted with
-    // the chains of the lane's VW points interleaved term by term (bitwise 1),
-    // 5 reassociated with the terms interleaved across the points (bitwise 2),
-    // 6 the same operations on explicit float pairs (wide lanes; bitwise 2):
-    // see upd_packed
-    static constexpr bool kPacked = FMA == 6;
-    static constexpr bool kFast = FMA == 2 || FMA == 3 || FMA == 5 || kPacked;
-    static constexpr bool kTermMajor = FMA == 4;
-    static constexpr bool kFastTM = FMA == 5;  // reassociated, terms issued across the lane's points
+    static constexpr bool kPacked = C.arith == kFastPacked;
+    static constexpr bool kFastTM = C.arith == kFastTermMajor;
+    static constexpr bool kFastAny = C.arith == kFast || kFastTM || kPacked;  // reassociated: the folded weights `fc`
+    static constexpr bool kTermMajor = C.arith == kFmaTermMajor;
+    static_assert(kFastAny || kTermMajor || C.arith == kExact || C.arith == kFma, "pipe: arith is a PipeArith");
     static_assert(!kPacked || (VW == 8 && sizeof(T) == 4 && ORDER == 8 && WPR == 1 && !LX),
                   "pipe: the packed-pair update is fp32, order 8, wide lanes, DPP x-neighbours");
     // kPacked: role 0 loads every input row straight into the window slot it
@@ -114,34 +130,74 @@ struct PipeN {
     VT nxt[PD][RB];     // role 0: input rows of the next PD phases, in flight (!kPacked)
     Ring* ring;         // ring[k]: step-(k+1) rows from role k to role k+1
     Edge* edge;         // edge[k]: seam lanes of the step-k rows role k received (WPR > 1)
-    const T* src;
+    const T* src;  // input and output rows at this lane's (clamped) column
     T* dst;
-    // OST = 1 / 2 (the dataflow launch's hand-off, heat_flow.hip): every
-    // output row / the rows outside [wt_lo, wt_hi) are stored write-through
-    // (sc1 buffer stores) from the uniform base `obase` at lane column `oxl`,
-    // so a completion flag needs no L2 write-back fence behind them for a
-    // reader on another XCD (cdna_hip_programming.md §6 Guideline 16, R1)
-    T* obase;
+    T* obase;  // ost: the output's uniform base, and this lane's column in it
     int oxl;
-    int wt_lo, wt_hi;  // OST = 2: rows outside [wt_lo, wt_hi) write-through, the rest as NT says
+    int wt_lo, wt_hi;  // ost = 2: rows outside [wt_lo, wt_hi) write-through, the rest as nt says
     int pitch, gy, xbase, lane, sub, glane, e3;
     int gl_l, gl_r;  // LX: the neighbour lanes (clamped into the strip; edge lanes are margin lanes)
     bool out_lane, full_vec;
     int y0, y1, xb, xe, xb1, xe1, yb1, ye1;
     T xcfl, ycfl;
-    HeatFast<ORDER, T> fc;  // kFast: folded weights, wave-uniform
+    HeatFast<ORDER, T> fc;  // kFastAny: folded weights, wave-uniform
     int r0, q;
+
+    // Role k's part of one task (pipe_task works out the arguments). The
+    // task's geometry comes in as scalars: handed over as one aggregate the
+    // kernels compile to another schedule (146 instead of 138 VGPRs on the
+    // fast pass, profiles/heat_pipe_cfg_r8.md).
+    static __device__ __forceinline__ void run_task(Ring* ring, Edge* edge, int k, int sub, const T* src, T* dst,
+                                                    int pitch, int gy, int xbase, int lane, bool out_lane,
+                                                    bool full_vec, int y0, int y1, int xb, int xe, int xb1, int xe1,
+                                                    int yb1, int ye1, T xcfl, T ycfl, T* obase, int oxl, int wt_lo,
+                                                    int wt_hi) {
+        PipeN st;
+        st.obase = obase;
+        st.oxl = oxl;
+        st.wt_lo = wt_lo;
+        st.wt_hi = wt_hi;
+        st.ring = ring;
+        st.edge = edge;
+        st.sub = sub;
+        st.glane = sub * 64 + lane;
+        st.gl_l = st.glane > 0 ? st.glane - 1 : 0;
+        st.gl_r = st.glane < LW - 1 ? st.glane + 1 : LW - 1;
+        st.src = src;
+        st.dst = dst;
+        st.pitch = pitch;
+        st.gy = gy;
+        st.xbase = xbase;
+        st.lane = lane;
+        st.out_lane = out_lane;
+        st.full_vec = full_vec;
+        st.y0 = y0;
+        st.y1 = y1;
+        st.xb = xb;
+        st.xe = xe;
+        st.xb1 = xb1;
+        st.xe1 = xe1;
+        st.yb1 = yb1;
+        st.ye1 = ye1;
+        st.xcfl = xcfl;
+        st.ycfl = ycfl;
+        if constexpr (kFastAny) {
+            const HeatFast<ORDER, T> f = heat_fast_coefs<ORDER>(xcfl, ycfl);
+            st.fc.c0 = uniform_f(f.c0);
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                st.fc.ax[i] = uniform_f(f.ax[i]);
+                st.fc.ay[i] = uniform_f(f.ay[i]);
+            }
+        }
+        st.run_role(k);
+    }
 
     __device__ __forceinline__ const T* row_ptr(int r) const {
         r = r < 0 ? 0 : (r >= gy ? gy - 1 : r);
         return src + (size_t)r * pitch;
     }
 
-    // One output row of VW columns. The x-neighbours beyond the lane are the
-    // B edge columns of the lanes on either side (DPP wave shifts; a wave
-    // seam of WPR > 1 takes the neighbour wave's value from `ev`). VW = 8
-    // moves 2B = 8 values per 8 points instead of per 4, and pairs more of the
-    // x operands inside one lane for the packed FMAs.
     // kPacked: one output row of 8 columns on explicit float pairs. The row
     // r[0..16) (4 halo + 8 own + 4 halo columns) is held as its 8 aligned
     // pairs E[m] = (r[2m], r[2m+1]) -- the own pairs are the window's
@@ -212,11 +268,17 @@ struct PipeN {
         return o;
     }
 
-    template <bool MASK, bool FROM_LDS = false, int WN = NW>
+    // One output row of VW columns from the window slots s_lo.. of a WN-slot
+    // window. The x-neighbours beyond the lane are the B edge columns of the
+    // lanes on either side (DPP wave shifts; a wave seam of WPR > 1 takes the
+    // neighbour wave's value from `ev`; FROM_LDS: the ring's xl / xr). VW = 8
+    // moves 2B = 8 values per 8 points instead of per 4, and pairs more of the
+    // x operands inside one lane for the packed FMAs.
+    template <bool MASK, int WN, bool FROM_LDS = false>
     __device__ __forceinline__ VT upd(int s_lo, int row, const V4<T>& ev, const V4<T>& xl = V4<T>{},
                                       const V4<T>& xr = V4<T>{}) const {
         if constexpr (kPacked) return upd_packed<MASK, WN>(s_lo, row);
-        const VT c = w[(s_lo + B) % NW];
+        const VT c = w[(s_lo + B) % WN];
         T rowv[VW + 2 * B];
         if constexpr (FROM_LDS) {  // the left lane's last B columns, the right lane's first B
 #pragma unroll
@@ -260,7 +322,7 @@ struct PipeN {
             for (int k = B - 1; k >= 0; --k)
 #pragma unroll
                 for (int j = 0; j < VW; ++j)
-                    u[j] = fmaT<T>(fc.ay[k], w[(s_lo + B + (k + 1)) % NW][j] + w[(s_lo + B - (k + 1)) % NW][j], u[j]);
+                    u[j] = fmaT<T>(fc.ay[k], w[(s_lo + B + (k + 1)) % WN][j] + w[(s_lo + B - (k + 1)) % WN][j], u[j]);
 #pragma unroll
             for (int j = 0; j < VW; ++j) {
                 if constexpr (MASK) {
@@ -280,8 +342,8 @@ struct PipeN {
                 for (int k = 0; k < B; ++k) {
                     xm[k][j] = rowv[B + j - (k + 1)];
                     xp[k][j] = rowv[B + j + (k + 1)];
-                    ym[k][j] = w[(s_lo + B - (k + 1)) % NW][j];
-                    yp[k][j] = w[(s_lo + B + (k + 1)) % NW][j];
+                    ym[k][j] = w[(s_lo + B - (k + 1)) % WN][j];
+                    yp[k][j] = w[(s_lo + B + (k + 1)) % WN][j];
                 }
             }
             heat_d2_fma_n<ORDER, VW>(dx, cc, xm, xp);
@@ -307,14 +369,14 @@ struct PipeN {
             for (int k = 0; k < B; ++k) {
                 xm[k] = rowv[B + j - (k + 1)];
                 xp[k] = rowv[B + j + (k + 1)];
-                ym[k] = w[(s_lo + B - (k + 1)) % NW][j];
-                yp[k] = w[(s_lo + B + (k + 1)) % NW][j];
+                ym[k] = w[(s_lo + B - (k + 1)) % WN][j];
+                yp[k] = w[(s_lo + B + (k + 1)) % WN][j];
             }
             T u;
-            if constexpr (kFast)
+            if constexpr (kFastAny)
                 u = heat_update_fast<ORDER>(c[j], xm, xp, ym, yp, fc);
             else
-                u = heat_update_sel<ORDER, FMA != 0>(c[j], xm, xp, ym, yp, xcfl, ycfl);
+                u = heat_update_sel<ORDER, C.arith != kExact>(c[j], xm, xp, ym, yp, xcfl, ycfl);
             if constexpr (MASK) {
                 const int x = xbase + j;
                 o[j] = (row_in && x >= xb1 && x < xe1) ? u : c[j];
@@ -416,20 +478,20 @@ struct PipeN {
                 if (row >= y0 - (NS - ST) * B && row < y1 + (NS - ST) * B) {
                     VT o;
                     if constexpr (LX && K > 0)
-                        o = upd<CHECK, true>((S + i) % WN, row, ev[i], ring[K - 1][cslot][i][NH - 1][gl_l],
-                                             ring[K - 1][cslot][i][0][gl_r]);
+                        o = upd<CHECK, WN, true>((S + i) % WN, row, ev[i], ring[K - 1][cslot][i][NH - 1][gl_l],
+                                                 ring[K - 1][cslot][i][0][gl_r]);
                     else
-                        o = upd<CHECK, false, WN>((S + i) % WN, row, ev[i]);
+                        o = upd<CHECK, WN>((S + i) % WN, row, ev[i]);
 #pragma unroll
                     for (int h = 0; h < NH; ++h) ring[K][par][i][h][glane] = piece4(o, h);
                 }
             } else if (row >= y0 && row < y1) {
                 VT o;
                 if constexpr (LX && K > 0)
-                    o = upd<false, true>((S + i) % WN, row, ev[i], ring[K - 1][cslot][i][NH - 1][gl_l],
-                                         ring[K - 1][cslot][i][0][gl_r]);
+                    o = upd<false, WN, true>((S + i) % WN, row, ev[i], ring[K - 1][cslot][i][NH - 1][gl_l],
+                                             ring[K - 1][cslot][i][0][gl_r]);
                 else
-                    o = upd<false, false, WN>((S + i) % WN, row, ev[i]);
+                    o = upd<false, WN>((S + i) % WN, row, ev[i]);
                 T* d = dst + (size_t)row * pitch;
                 bool wt = false;
                 if constexpr (OST != 0) wt = OST == 1 || row < wt_lo || row >= wt_hi;
@@ -515,71 +577,23 @@ struct PipeN {
     }
 };
 
-template <typename T, int ORDER, int RB, int NS, int FMA, bool CHECK, int PD, bool NT, int WPR, int VW, bool LX,
-          int NSLOT, int OST = 0>
-__device__ __forceinline__ void pipen_run(V4<T> (*ring)[NSLOT][RB][VW / 4][64 * WPR], V4<T> (*edge)[3][RB][WPR][2],
-                                          int k, int sub, const T* src, T* dst, int pitch, int gy, int xbase,
-                                          int lane, bool out_lane, bool full_vec, int y0, int y1, int xb, int xe,
-                                          int xb1, int xe1, int yb1, int ye1, T xcfl, T ycfl, T* obase = nullptr,
-                                          int oxl = 0, int wt_lo = 0, int wt_hi = 0) {
-    PipeN<T, ORDER, RB, NS, FMA, CHECK, PD, NT, WPR, VW, LX, OST> st;
-    static_assert(decltype(st)::NSLOT == NSLOT, "pipe: ring slots");
-    st.obase = obase;
-    st.oxl = oxl;
-    st.wt_lo = wt_lo;
-    st.wt_hi = wt_hi;
-    st.ring = ring;
-    st.edge = edge;
-    st.sub = sub;
-    st.glane = sub * 64 + lane;
-    st.gl_l = st.glane > 0 ? st.glane - 1 : 0;
-    st.gl_r = st.glane < 64 * WPR - 1 ? st.glane + 1 : 64 * WPR - 1;
-    st.src = src;
-    st.dst = dst;
-    st.pitch = pitch;
-    st.gy = gy;
-    st.xbase = xbase;
-    st.lane = lane;
-    st.out_lane = out_lane;
-    st.full_vec = full_vec;
-    st.y0 = y0;
-    st.y1 = y1;
-    st.xb = xb;
-    st.xe = xe;
-    st.xb1 = xb1;
-    st.xe1 = xe1;
-    st.yb1 = yb1;
-    st.ye1 = ye1;
-    st.xcfl = xcfl;
-    st.ycfl = ycfl;
-    if constexpr (decltype(st)::kFast) {
-        const HeatFast<ORDER, T> f = heat_fast_coefs<ORDER>(xcfl, ycfl);
-        st.fc.c0 = uniform_f(f.c0);
-#pragma unroll
-        for (int i = 0; i < HeatOrder<ORDER>::B; ++i) {
-            st.fc.ax[i] = uniform_f(f.ax[i]);
-            st.fc.ay[i] = uniform_f(f.ay[i]);
-        }
-    }
-    st.run_role(k);
-}
-
 // One strip-chunk task of region r of R (the whole workgroup): rows and
 // columns of the task, the interior / edge instantiation, the pass itself.
 // Shared by the one-pass launch (heat_pipe_kernel) and the persistent
 // multi-pass dataflow launch (heat_flow.hip).
-template <typename T, int ORDER, int RB, int NS, int FMA, int PD, bool NT, int WPR, int VW, bool LX, int NSLOT,
-          int OST = 0>
-__device__ __forceinline__ void pipe_task(V4<T> (*ring)[NSLOT][RB][VW / 4][64 * WPR],
-                                          V4<T> (*edge)[3][RB][WPR][2], const S2Regions& R, int r, int task,
+// ring / edge: the workgroup's LDS, PipeN<T, C, *>::Ring[ns - 1] and
+// ::Edge[wpr > 1 ? ns : 1] (the same types for both CHECK instantiations).
+template <typename T, PipeCfg C>
+__device__ __forceinline__ void pipe_task(typename PipeN<T, C, false>::Ring* ring,
+                                          typename PipeN<T, C, false>::Edge* edge, const S2Regions& R, int r, int task,
                                           const T* prev, T* curr, int pitch, int gy, int xb1, int xe1, int yb1,
                                           int ye1, T xcfl, T ycfl, int k, int sub, int lane, int wt_lo = 0,
                                           int wt_hi = 0) {
-    constexpr int B = HeatOrder<ORDER>::B;
-    using G = PipeOut<NS, WPR, VW, B>;
-    constexpr int OUT = G::kOut;
-    constexpr int M = G::kMargin;
-    constexpr int LW = 64 * WPR;
+    constexpr int NS = C.ns, VW = C.vw;
+    constexpr int B = HeatOrder<C.order>::B;
+    constexpr int OUT = PipeOut<C>::kOut;
+    constexpr int M = PipeOut<C>::kMargin;
+    constexpr int LW = 64 * C.wpr;
     const int xb = R.xb[r], xe = R.xe[r], yb = R.yb[r], ye = R.ye[r];
     const int strips = R.strips[r];
     // chunk word: rows per chunk in the low 16 bits; a tapered region
@@ -601,28 +615,30 @@ __device__ __forceinline__ void pipe_task(V4<T> (*ring)[NSLOT][RB][VW / 4][64 * 
     const bool inside = (xs - reach >= xb1) && (xs + OUT + reach <= xe1) && (y0 - (NS - 1) * B >= yb1) &&
                         (y1 + (NS - 1) * B <= ye1) && (xs >= xb) && (xs + OUT <= xe);
     if (inside)
-        pipen_run<T, ORDER, RB, NS, FMA, false, PD, NT, WPR, VW, LX, NSLOT, OST>(
-            ring, edge, k, sub, prev + xl, curr + xl, pitch, gy, xbase, lane, out_lane, full_vec, y0, y1, xb, xe, xb1,
-            xe1, yb1, ye1, xcfl, ycfl, curr, xl, wt_lo, wt_hi);
+        PipeN<T, C, false>::run_task(ring, edge, k, sub, prev + xl, curr + xl, pitch, gy, xbase, lane, out_lane,
+                                     full_vec, y0, y1, xb, xe, xb1, xe1, yb1, ye1, xcfl, ycfl, curr, xl, wt_lo, wt_hi);
     else
-        pipen_run<T, ORDER, RB, NS, FMA, true, PD, NT, WPR, VW, LX, NSLOT, OST>(
-            ring, edge, k, sub, prev + xl, curr + xl, pitch, gy, xbase, lane, out_lane, full_vec, y0, y1, xb, xe, xb1,
-            xe1, yb1, ye1, xcfl, ycfl, curr, xl, wt_lo, wt_hi);
+        PipeN<T, C, true>::run_task(ring, edge, k, sub, prev + xl, curr + xl, pitch, gy, xbase, lane, out_lane,
+                                    full_vec, y0, y1, xb, xe, xb1, xe1, yb1, ye1, xcfl, ycfl, curr, xl, wt_lo, wt_hi);
 }
 
-// one workgroup (NS roles x WPR waves) per strip-chunk task; regions as for
-// streamN. VW = 8: strips start on 8-column boundaries, so every lane's
+// threads per workgroup, and the workgroups per CU that occ waves per SIMD
+// make (__launch_bounds__ of every kernel that runs pipe_task)
+constexpr int pipe_threads(PipeCfg c) { return c.ns * c.wpr * 64; }
+constexpr int pipe_min_blocks(PipeCfg c) { return c.occ > 0 ? 4 * c.occ / c.ns : 1; }
+
+// one workgroup (ns roles x wpr waves) per strip-chunk task; regions as for
+// streamN. vw = 8: strips start on 8-column boundaries, so every lane's
 // columns lie wholly inside or wholly outside the grid (the edge lanes' loads
 // are clamped into the row).
-template <typename T, int ORDER, int RB, int NS, int FMA, int PD = 1, bool NT = false, int WPR = 1, int VW = 4,
-          int OCC = (FMA == 3 ? 4 : 0), bool LX = false>
-__global__ __launch_bounds__(NS * WPR * 64, (OCC > 0 ? 4 * OCC / NS : 1)) void heat_pipe_kernel(
+template <typename T, PipeCfg C>
+__global__ __launch_bounds__(pipe_threads(C), pipe_min_blocks(C)) void heat_pipe_kernel(
     const T* __restrict__ prev, T* __restrict__ curr, int pitch, int gy, S2Regions R, int xb1, int xe1, int yb1,
     int ye1, T xcfl, T ycfl, PipeGate gate) {
-    static_assert(NS >= 2 && NS <= 6, "pipe: 2..6 steps per pass");
-    constexpr int NSLOT = PipeN<T, ORDER, RB, NS, FMA, false, PD, NT, WPR, VW, LX>::NSLOT;
-    __shared__ V4<T> ring[NS - 1][NSLOT][RB][VW / 4][64 * WPR];
-    __shared__ V4<T> edge[WPR > 1 ? NS : 1][3][RB][WPR][2];
+    constexpr int WPR = C.wpr;
+    constexpr PipeCfg CB = uncapped(C);  // the body's config
+    __shared__ typename PipeN<T, CB, false>::Ring ring[C.ns - 1];
+    __shared__ typename PipeN<T, CB, false>::Edge edge[WPR > 1 ? C.ns : 1];
     const int lane = lane_id();
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
     const int k = wv / WPR, sub = wv % WPR;
@@ -654,8 +670,7 @@ __global__ __launch_bounds__(NS * WPR * 64, (OCC > 0 ? 4 * OCC / NS : 1)) void h
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // the halo rows the exchange wrote, not stale L1 lines
     }
-    pipe_task<T, ORDER, RB, NS, FMA, PD, NT, WPR, VW, LX, NSLOT>(ring, edge, R, r, task, prev, curr, pitch, gy, xb1, xe1,
-                                                             yb1, ye1, xcfl, ycfl, k, sub, lane);
+    pipe_task<T, CB>(ring, edge, R, r, task, prev, curr, pitch, gy, xb1, xe1, yb1, ye1, xcfl, ycfl, k, sub, lane);
     if (gate.trace) {  // profiling: the whole workgroup's span (vector stores)
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -682,8 +697,9 @@ __global__ __launch_bounds__(NS * WPR * 64, (OCC > 0 ? 4 * OCC / NS : 1)) void h
 // on one N = 4 / 8 rank (profiles/dist_rank_trace_r4.md): every task then
 // starts at once, but the pass got 5 / 2 % SLOWER (the span is set by the
 // slowest interior tasks, which got taller), so launch_pipe_multi passes 0.
-template <int NS, int RB, int VW = 4>
+template <PipeCfg C>
 int pipe_chunk(int strips, int H, int chunk_hint, int per_cu_hint, long resident, bool thin_floor, long reserve = 0) {
+    constexpr int RB = C.rb, VW = C.vw;
     const int env_chunk = (int)cme::tune_get(cme::kTunePipeChunk);
     const int env_per_cu = (int)cme::tune_get(cme::kTunePipePerCU);
     const int thin_min = (int)cme::tune_get(cme::kTunePipeThinMin);
@@ -733,16 +749,62 @@ int pipe_chunk(int strips, int H, int chunk_hint, int per_cu_hint, long resident
     return ((chunk + RB - 1) / RB) * RB;
 }
 
-template <typename T, int ORDER, int NS, int FMA, int RB, int PD = 1, bool NT = false, int WPR = 1, int VW = 4,
-          int OCC = (FMA == 3 ? 4 : 0), bool LX = false>
+// The production pass (cme_heat_pipe_*, heat_pipe.hip) of element type T at
+// one stencil order and arithmetic (fma: FMA-contracted, else exact); `ns` is
+// set per launch with with().
+//
+// fp32 wide (the default at order 8): 8 columns per lane, 2 rows per phase
+// (156 VGPRs, 3 waves per SIMD), the FMA chains of a lane's 8 points
+// interleaved (bitwise kFma), one phase of input loads in flight,
+// non-temporal output stores: 0.1308 vs 0.1417 ms/step for the round-2
+// 4-column pass (rb 4) on the bench's 16384^2 field (benchmarks/
+// tune_heat_pipe.py, profiles/heat_pipe_wide_r3.md). Orders 2 / 4 keep 4
+// columns per lane (faster on the 4000^2 rows there).
+//
+// fp64: the same pass on doubles (32 B per lane per row; 2 rows per phase
+// keeps the window + prefetch within ~128 VGPRs). The hw5 workload is double
+// precision (hw/hw5/2dHeat_solution.cpp:63-84). (A term-major chain order,
+// the fp32 wide pass's, was measured here on the hw5 shapes: 1000^2 / 2000^2 /
+// 4000^2, orders 4 and 8, within 1 % of this chain-major order -- profiles/
+// heat_tile_r4.md -- and removed.)
+template <typename T>
+constexpr PipeCfg pipe_prod_cfg(int order, bool fma, bool wide = false) {
+    if (sizeof(T) == 8) return {.order = order, .arith = fma ? kFma : kExact, .rb = 2};
+    if (wide) return {.order = order, .arith = fma ? kFmaTermMajor : kExact, .rb = 2, .nt = true, .vw = 8};
+    return {.order = order, .arith = fma ? kFma : kExact, .rb = 4, .nt = true};
+}
+
+// poll bound of the fused schedule's gated border workgroups (PipeGate):
+// CME_DIST_GATE_SPINS, read per call (a test forces the timeout path in-process)
+inline unsigned gate_spin_limit() {
+    const long v = cme::tune_get(cme::kTuneDistGateSpins);
+    return v > 0 ? (unsigned)v : (1u << 24);
+}
+
+// the gate of regions [wait_from, n) on *flag >= value; flag == nullptr: none
+inline PipeGate make_gate(const unsigned* flag, unsigned value, int wait_from, unsigned* timeout) {
+    PipeGate gate;
+    if (flag) {
+        gate.flag = flag;
+        gate.val = value;
+        gate.from = wait_from;
+        gate.timeout = timeout;
+        gate.spins = gate_spin_limit();
+    }
+    return gate;
+}
+
+template <typename T, PipeCfg C>
 int launch_pipe_multi(const T* prev, T* curr, int pitch, int gy, const Region* gs, int n, Region g1, T xcfl, T ycfl,
                       int chunk_hint, int per_cu, hipStream_t s, PipeGate gate = PipeGate{}) {
     if (n < 1 || n > kMaxS2Regions) return (int)hipErrorInvalidValue;
     if ((pitch & 63) != 0) return (int)hipErrorInvalidValue;
+    constexpr int RB = C.rb, VW = C.vw;
     static const long resident = [] {
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, heat_pipe_kernel<T, ORDER, RB, NS, FMA, PD, NT, WPR, VW, OCC, LX>,
-                                                         NS * WPR * 64, 0) != hipSuccess || per_cu < 1)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, heat_pipe_kernel<T, C>, pipe_threads(C), 0) !=
+                hipSuccess ||
+            per_cu < 1)
             per_cu = 1;
         return (long)per_cu * device_cu_count();
     }();
@@ -750,7 +812,7 @@ int launch_pipe_multi(const T* prev, T* curr, int pitch, int gy, const Region* g
     int tasks = 0;
     const int gate_from = gate.from;
     gate.from = kMaxS2Regions;  // region index in R of the first gated input region
-    constexpr int kOut = PipeOut<NS, WPR, VW, HeatOrder<ORDER>::B>::kOut;
+    constexpr int kOut = PipeOut<C>::kOut;
     const long reserve = 0;  // see pipe_chunk
     for (int i = 0; i < n; ++i) {
         const Region& g = gs[i];
@@ -758,7 +820,7 @@ int launch_pipe_multi(const T* prev, T* curr, int pitch, int gy, const Region* g
         if (i >= gate_from && gate.from == kMaxS2Regions) gate.from = R.n;
         if (H <= 0 || g.xe <= g.xb) continue;
         const int strips = (int)cdiv(g.xe - (g.xb & ~(VW - 1)), kOut);
-        int chunk = pipe_chunk<NS, RB, VW>(strips, H, chunk_hint, per_cu, resident, n > 1, reserve);
+        int chunk = pipe_chunk<C>(strips, H, chunk_hint, per_cu, resident, n > 1, reserve);
         int nchunks = (int)cdiv(H, chunk), n1 = 0;
         // taper (pipe_taper): a region of several rounds of resident tasks
         // ends in shorter tasks, so the last round drains sooner (the
@@ -792,7 +854,7 @@ int launch_pipe_multi(const T* prev, T* curr, int pitch, int gy, const Region* g
         const long gated = tasks - (gate.from > 0 ? R.wave_end[gate.from - 1] : 0);
         if (2 * gated > resident) return (int)hipErrorInvalidConfiguration;
     }
-    hipLaunchKernelGGL((heat_pipe_kernel<T, ORDER, RB, NS, FMA, PD, NT, WPR, VW, OCC, LX>), dim3(tasks), dim3(NS * WPR * 64), 0, s,
-                       prev, curr, pitch, gy, R, g1.xb, g1.xe, g1.yb, g1.ye, xcfl, ycfl, gate);
+    hipLaunchKernelGGL((heat_pipe_kernel<T, C>), dim3(tasks), dim3(pipe_threads(C)), 0, s, prev, curr, pitch, gy, R,
+                       g1.xb, g1.xe, g1.yb, g1.ye, xcfl, ycfl, gate);
     CME_LAUNCH_STATUS();
 }

@@ -76,16 +76,17 @@ struct FlowArgs {
     unsigned long long* trace;  // profiling: per ticket {ticket time, start, end, HW_ID | XCC_ID << 32}
 };
 
-// OST: output stores of the pipelined task, 0 non-temporal (every task then
+// C.ost: output stores of the pipelined task, 0 non-temporal (every task then
 // needs a release fence), 2 non-temporal except the band-edge rows (write-
 // through)
-template <typename T, int ORDER, int RB, int NS, int FMA, int PD, bool NT, int WPR, int VW, int OCC, int OST>
-__global__ __launch_bounds__(NS * WPR * 64, (OCC > 0 ? 4 * OCC / NS : 1)) void heat_flow_kernel(
+template <typename T, PipeCfg C>
+__global__ __launch_bounds__(pipe_threads(C), pipe_min_blocks(C)) void heat_flow_kernel(
     T* a, T* b, int pitch, int gy, S2Regions R, int xb1, int xe1, int yb1, int ye1, T xcfl, T ycfl, FlowArgs f) {
-    constexpr int NSLOT = PipeN<T, ORDER, RB, NS, FMA, false, PD, NT, WPR, VW, false>::NSLOT;
-    constexpr int B = HeatOrder<ORDER>::B;
-    __shared__ V4<T> ring[NS - 1][NSLOT][RB][VW / 4][64 * WPR];
-    __shared__ V4<T> edge[WPR > 1 ? NS : 1][3][RB][WPR][2];
+    constexpr int NS = C.ns, WPR = C.wpr, OST = C.ost;
+    constexpr int B = HeatOrder<C.order>::B;
+    constexpr PipeCfg CB = uncapped(C);  // the body's config
+    __shared__ typename PipeN<T, CB, false>::Ring ring[NS - 1];
+    __shared__ typename PipeN<T, CB, false>::Edge edge[WPR > 1 ? NS : 1];
     __shared__ int s_ticket, s_stop;
     const int lane = lane_id();
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
@@ -187,8 +188,8 @@ __global__ __launch_bounds__(NS * WPR * 64, (OCC > 0 ? 4 * OCC / NS : 1)) void h
         if (f.trace && threadIdx.x == 0) t_start = wall_clock64();
         T* src = (pass & 1) ? b : a;
         T* dst = (pass & 1) ? a : b;
-        pipe_task<T, ORDER, RB, NS, FMA, PD, NT, WPR, VW, false, NSLOT, OST>(
-            ring, edge, R, 0, task, src, dst, pitch, gy, xb1, xe1, yb1, ye1, xcfl, ycfl, k, sub, lane, wt_lo, wt_hi);
+        pipe_task<T, CB>(ring, edge, R, 0, task, src, dst, pitch, gy, xb1, xe1, yb1, ye1, xcfl, ycfl, k, sub, lane,
+                         wt_lo, wt_hi);
         // publish: every wave drains its stores (and its last loads of the
         // input this pass's successors overwrite), barrier, one lane stores
         // the completion word
@@ -252,19 +253,19 @@ int xcd_bands_ok(bool* ok) {
 
 constexpr size_t kCtlWords = kCtlStride * (kBands + 1);
 
-template <typename T, int ORDER, int NS, int FMA, int RB, int PD, bool NT, int WPR, int VW, int OCC, int OST>
+template <typename T, PipeCfg C>
 int launch_flow(T* a, T* b, int pitch, int gy, Region g, T xcfl, T ycfl, int npass, hipStream_t s,
                 unsigned long long* trace, int* ntasks_out) {
-    constexpr int B = HeatOrder<ORDER>::B;
-    constexpr int kOut = PipeOut<NS, WPR, VW, B>::kOut;
+    constexpr int NS = C.ns, RB = C.rb, VW = C.vw;
+    constexpr int B = HeatOrder<C.order>::B;
+    constexpr int kOut = PipeOut<C>::kOut;
     static_assert(kOut >= 16, "flow: the strip neighbourhood must cover the pass's column reach");
     if (npass < 1) return 0;
     if ((pitch & 63) != 0) return (int)hipErrorInvalidValue;
     if ((size_t)gy * pitch * sizeof(T) >= (1ull << 31)) return (int)hipErrorInvalidValue;  // 32-bit store offsets
     static const long resident = [] {
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &per_cu, heat_flow_kernel<T, ORDER, RB, NS, FMA, PD, NT, WPR, VW, OCC, OST>, NS * WPR * 64, 0) !=
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, heat_flow_kernel<T, C>, pipe_threads(C), 0) !=
                 hipSuccess ||
             per_cu < 1)
             per_cu = 1;
@@ -274,7 +275,7 @@ int launch_flow(T* a, T* b, int pitch, int gy, Region g, T xcfl, T ycfl, int npa
     if (H <= 0 || g.xe <= g.xb) return 0;
     const int strips = (int)cdiv(g.xe - (g.xb & ~(VW - 1)), kOut);
     const int per_cu = (int)cme::tune_get(cme::kTuneFlowPerCU);
-    int chunk = pipe_chunk<NS, RB, VW>(strips, H, 0, per_cu, resident, false);
+    int chunk = pipe_chunk<C>(strips, H, 0, per_cu, resident, false);
     // the 3 x 3 neighbourhood covers a task's row reach only for chunks of
     // at least NS*B rows (a whole-height chunk has no row neighbours at all);
     // a band edge's write-through rows need two of them
@@ -317,17 +318,19 @@ int launch_flow(T* a, T* b, int pitch, int gy, Region g, T xcfl, T ycfl, int npa
     // them; fewer workgroups than the resident count would idle CUs)
     const long grid = resident;
     if (ntasks_out) *ntasks_out = (int)tpp;
-    hipLaunchKernelGGL((heat_flow_kernel<T, ORDER, RB, NS, FMA, PD, NT, WPR, VW, OCC, OST>), dim3((unsigned)grid),
-                       dim3(NS * WPR * 64), 0, s, a, b, pitch, gy, R, g.xb, g.xe, g.yb, g.ye, xcfl, ycfl, f);
+    hipLaunchKernelGGL((heat_flow_kernel<T, C>), dim3((unsigned)grid), dim3(pipe_threads(C)), 0, s, a, b, pitch, gy, R,
+                       g.xb, g.xe, g.yb, g.ye, xcfl, ycfl, f);
     CME_LAUNCH_STATUS();
 }
 
-// the production pass of each arithmetic (fp32, order 8, wide lanes, RB = 2,
-// non-temporal stores; heat_pipe.hip / heat_fast.hip): exact (FMA arm 0),
-// FMA-contracted with term-major chains (4), reassociated with its terms
-// interleaved across the lane's points (5); registers capped for 3 waves per
-// SIMD
-template <int FMA>
+// the production pass of each arithmetic (fp32, order 8, four steps, wide
+// lanes, rb = 2, non-temporal stores; heat_pipe.hip / heat_fast.hip): kExact,
+// kFmaTermMajor, kFastTermMajor; registers capped for 3 waves per SIMD
+constexpr PipeCfg flow_cfg(int arith, int ost) {
+    return {.ns = 4, .arith = arith, .rb = 2, .nt = true, .vw = 8, .occ = 3, .ost = ost};
+}
+
+template <int ARITH>
 int flow_arith(float* a, float* b, int pitch, int gy, Region g, float xcfl, float ycfl, int npass, hipStream_t s,
                unsigned long long* trace, int* ntasks) {
     bool bands = false;
@@ -338,19 +341,17 @@ int flow_arith(float* a, float* b, int pitch, int gy, Region g, float xcfl, floa
     // diagnostics (mode 4096), or not the 8 XCC_IDs the bands need: one
     // queue, a release fence per task
     if (!bands || (cme::tune_get(cme::kTuneFlowMode) & 4096))
-        return launch_flow<float, 8, 4, FMA, 2, 1, true, 1, 8, 3, 0>(a, b, pitch, gy, g, xcfl, ycfl, npass, s, trace,
-                                                                    ntasks);
-    return launch_flow<float, 8, 4, FMA, 2, 1, true, 1, 8, 3, 2>(a, b, pitch, gy, g, xcfl, ycfl, npass, s, trace,
-                                                                ntasks);
+        return launch_flow<float, flow_cfg(ARITH, 0)>(a, b, pitch, gy, g, xcfl, ycfl, npass, s, trace, ntasks);
+    return launch_flow<float, flow_cfg(ARITH, 2)>(a, b, pitch, gy, g, xcfl, ycfl, npass, s, trace, ntasks);
 }
 
 int flow_f32(float* a, float* b, int pitch, int gy, Region g, int arith, int ns, float xcfl, float ycfl, int npass,
              hipStream_t s, unsigned long long* trace, int* ntasks) {
     if (ns != 4) return (int)hipErrorInvalidValue;
     switch (arith) {
-        case 0: return flow_arith<0>(a, b, pitch, gy, g, xcfl, ycfl, npass, s, trace, ntasks);
-        case 1: return flow_arith<4>(a, b, pitch, gy, g, xcfl, ycfl, npass, s, trace, ntasks);
-        case 2: return flow_arith<5>(a, b, pitch, gy, g, xcfl, ycfl, npass, s, trace, ntasks);
+        case 0: return flow_arith<kExact>(a, b, pitch, gy, g, xcfl, ycfl, npass, s, trace, ntasks);
+        case 1: return flow_arith<kFmaTermMajor>(a, b, pitch, gy, g, xcfl, ycfl, npass, s, trace, ntasks);
+        case 2: return flow_arith<kFastTermMajor>(a, b, pitch, gy, g, xcfl, ycfl, npass, s, trace, ntasks);
         default: return (int)hipErrorInvalidValue;
     }
 }
@@ -400,5 +401,5 @@ CME_EXPORT int cme_heat_flow_status(unsigned* timed_out, int reset) {
 }
 
 // kernels in the occupancy / resource report (cme_kernel_query)
-CME_REGISTER_KERNEL(heat_flow4_fma_f32_o8, 256, heat_flow_kernel<float, 8, 2, 4, 4, 1, true, 1, 8, 3, 2>);
-CME_REGISTER_KERNEL(heat_flow4_fast_f32_o8, 256, heat_flow_kernel<float, 8, 2, 4, 5, 1, true, 1, 8, 3, 2>);
+CME_REGISTER_KERNEL(heat_flow4_fma_f32_o8, 256, heat_flow_kernel<float, flow_cfg(kFmaTermMajor, 2)>);
+CME_REGISTER_KERNEL(heat_flow4_fast_f32_o8, 256, heat_flow_kernel<float, flow_cfg(kFastTermMajor, 2)>);

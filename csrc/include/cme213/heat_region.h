@@ -23,21 +23,19 @@ struct S2Regions {
     int wave_end[kMaxS2Regions];  // cumulative wave (or workgroup-task) counts
 };
 
+// The nout regions {xb, xe, yb, ye} a C entry point receives as ints, into
+// gs[kMaxS2Regions]; false if there are none or too many.
+inline bool regions_from(const int* out, int nout, Region* gs) {
+    if (nout < 1 || nout > kMaxS2Regions) return false;
+    for (int i = 0; i < nout; ++i) gs[i] = Region{out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]};
+    return true;
+}
+
 // Output columns of one 64-lane strip of an NS-step pass (4 columns per lane;
 // step k is valid on lanes k..63-k, x-neighbours arrive through DPP).
 template <int NS>
 struct StripN {
     static constexpr int kOut = (64 - 2 * NS) * 4;
-};
-
-// Output columns of one strip of the wave-pipelined pass: WPR waves side by
-// side per timestep role (64*WPR lanes of VW columns). VW = 4: NS lanes lost
-// per side (one lane per step, exact at order 8). VW = 8 (wide lanes): the
-// whole lanes covering the NS*B columns each side loses over NS steps.
-template <int NS, int WPR, int VW = 4, int B = 4>
-struct PipeOut {
-    static constexpr int kMargin = VW == 4 ? NS : (NS * B + VW - 1) / VW;
-    static constexpr int kOut = (64 * WPR - 2 * kMargin) * VW;
 };
 
 // Fused-schedule gate of the pipelined pass: workgroups of regions

@@ -115,7 +115,7 @@ def check_asm(asm: str, src: str) -> list[dict]:
 def compile_asm(src: str) -> str:
     with tempfile.TemporaryDirectory() as d:
         s = os.path.join(d, "k.s")
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics",
+        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++20", "-munsafe-fp-atomics",
                         f"-I{os.path.join(REPO, 'csrc', 'include')}", "--cuda-device-only", "-S", src, "-o", s],
                        check=True, capture_output=True)
         with open(s) as f:
