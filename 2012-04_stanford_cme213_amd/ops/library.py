@@ -14,6 +14,7 @@ Ops (schema in each docstring; "!" = mutated in place):
 ``heat_step``             curr![region] = FTCS(prev)           (hw2 kernels, any variant)
 ``heat_stepn``            nsteps (2-4) timesteps in one HBM pass (temporal blocking)
 ``scan``                  inclusive / exclusive prefix sum
+``scan_op``               inclusive / exclusive prefix sum / running max / running min
 ``segmented_scan``        inclusive segmented sum scan (uint8 heads or int32 bitmask)
 ``sort`` / ``sort_by_key`` stable LSD radix sort, 32- and 64-bit keys (+ 4- / 8-byte values)
 ``argsort``               int64 stable sorting permutation (ascending or descending)
@@ -87,6 +88,17 @@ def scan(x: Tensor, exclusive: bool = False) -> Tensor:
 
 @scan.register_fake
 def _(x, exclusive=False):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op(f"{NS}::scan_op", mutates_args=())
+def scan_op(x: Tensor, op: str, exclusive: bool = False) -> Tensor:
+    """scan_op(Tensor x, str op, bool exclusive) -> Tensor   (op: "sum", "max", "min")"""
+    return _fresh(_scan.scan(x, exclusive=exclusive, op=op), x)
+
+
+@scan_op.register_fake
+def _(x, op, exclusive=False):
     return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 
@@ -198,7 +210,8 @@ def _(x, flags):
 
 
 OPS = {
-    "heat_step": heat_step, "heat_stepn": heat_stepn, "scan": scan, "segmented_scan": segmented_scan,
+    "heat_step": heat_step, "heat_stepn": heat_stepn, "scan": scan, "scan_op": scan_op,
+    "segmented_scan": segmented_scan,
     "sort": sort, "sort_by_key": sort_by_key, "argsort": argsort, "spmv_csr": spmv_csr, "transpose": transpose, "sgemm": sgemm,
     "gemv": gemv, "copy_if": copy_if,
 }

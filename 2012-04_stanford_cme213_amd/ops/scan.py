@@ -3,6 +3,9 @@
 * :func:`scan` -- single-pass decoupled look-back (default) or the lecture's
   multi-level scan-then-add with a Blelloch or Hillis-Steele block algorithm
   (``slides/Lecture16.pdf``; ``my-refs/scan.pdf`` Fig. 5).
+* :func:`cummax` / :func:`cummin` (``scan(..., op="max" / "min")``) -- the
+  running maximum / minimum, ``torch.cummax`` / ``torch.cummin`` values bit for
+  bit, with ``algo="lookback"`` or ``"rts"``.
 * :func:`reduce` -- sum / max / min; the lecture's shared-memory tree
   (``slides/Lecture05.pdf`` 15-16) as ``algo="tree"``.
 * Both take float32 / int32 and int64 / float64 (``scan`` also uint32); the
@@ -29,7 +32,11 @@ _ext.proto(_ext.HIP_PROTOS, "cme_scan_tree", "ppqiiipp")
 _ext.proto(_ext.HIP_PROTOS, "cme_reduce", "pqiiippp")
 _ext.proto(_ext.HIP_PROTOS, "cme_segscan", "ppppiqpup")
 _ext.proto(_ext.HIP_PROTOS, "cme_spmv_scan_run", "pppqipp")
+_ext.proto(_ext.HIP_PROTOS, "cme_scan_op", "ppqiiipup")
+_ext.proto(_ext.HIP_PROTOS, "cme_scan_rts_op", "ppqiiipp")
+_ext.proto(_ext.HIP_PROTOS, "cme_scan_op_info", "qiiip")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_scan", "ppqii")
+_ext.proto(_ext.CPU_PROTOS, "cme_cpu_scan_op", "ppqiii")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_reduce", "pqiip")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_segscan", "ppppiq")
 
@@ -47,6 +54,16 @@ _VECTOR_ALGOS = ("lookback", "rts", "blelloch", "hillis")  # 32-bit: 16-byte loa
 # both 2^25 and 2^27 elements (benchmarks/bench_primitives.py --only scan64,
 # profiles/scan64_r8.md)
 _AUTO_INT64 = "lookback"
+# max / min scans: "rts" and "lookback" only, every dtype. Their operator is
+# exactly associative on floats too, so the single-pass look-back is bitwise
+# reproducible and "auto" is "lookback" for every dtype. Measured
+# (benchmarks/bench_primitives.py --only scan_minmax, profiles/scan_minmax.md):
+# the look-back is the faster arm at 2^25 and 2^27 for int32, int64 and float64
+# and at 2^27 for float32; float32 at 2^25 has "rts" ahead (0.081 against 0.091
+# ms) inside the spread of both arms, which does not earn a size switch.
+_ALGOS_MINMAX = ("rts", "lookback")
+_AUTO_MINMAX = {torch.float32: "lookback", torch.int32: "lookback", torch.uint32: "lookback",
+                torch.int64: "lookback", torch.float64: "lookback"}
 
 _ws_cache: dict = {}
 
@@ -107,17 +124,41 @@ _ext.proto(_ext.HIP_PROTOS, "cme_scan32_info", "qiiip")
 _SCAN32_KINDS = {"lookback": 0, "segscan": 1}
 
 
+_OP_INFO_KEYS = ("tile", "tiles", "workgroups", "blocks_per_cu", "rts_chunks", "rts_tiles_per_chunk", "rts_tile",
+                 "lookback_ws_bytes")
+
+
+def _scan_op_info(n: int, dtype: torch.dtype, op: str, exclusive: bool, device) -> dict:
+    """``cme_scan_op_info``: the launch shape of the kernels of (dtype, op,
+    exclusive) -- the max / min kernels are instantiations of their own."""
+    import ctypes
+
+    if op not in _OPS:
+        raise ValueError(f"scan: op {op!r} is not one of {sorted(_OPS)}")
+    info = (ctypes.c_longlong * 8)()
+    code = _DT64[dtype] if dtype in _DT64 else _DT_SCAN[dtype]
+    with torch.cuda.device(torch.device(device)):
+        _ext.call_hip("cme_scan_op_info", n, code, _OPS[op], int(exclusive), ctypes.addressof(info))
+    return dict(zip(_OP_INFO_KEYS, (int(v) for v in info)))
+
+
 def scan_launch_info(n: int, kind: str = "lookback", exclusive: bool = False, device: torch.device | str = "cuda",
-                     dtype: torch.dtype = torch.float32) -> dict:
+                     dtype: torch.dtype = torch.float32, op: str = "sum") -> dict:
     """How a 32-bit look-back launch of ``n`` elements is shaped on ``device``:
     ``tile`` (elements), ``tiles``, ``workgroups`` (the persistent, co-resident
     grid) and ``blocks_per_cu``. ``kind``: "lookback" (:func:`scan` with
-    ``algo="lookback"``; ``exclusive`` and ``dtype`` pick the kernel) or
-    "segscan" (the float32 :func:`segmented_scan`)."""
+    ``algo="lookback"``; ``exclusive``, ``dtype`` and ``op`` pick the kernel) or
+    "segscan" (the float32 :func:`segmented_scan`). With ``op="max"`` /
+    ``"min"`` the dict also has ``rts_chunks``, ``rts_tiles_per_chunk`` and
+    ``rts_tile`` of ``algo="rts"``, and ``lookback_ws_bytes``."""
     import ctypes
 
     if kind not in _SCAN32_KINDS:
         raise ValueError(f"scan_launch_info: kind {kind!r} is not one of {sorted(_SCAN32_KINDS)}")
+    if op != "sum":
+        if kind != "lookback":
+            raise ValueError("scan_launch_info: only the plain scans take an op")
+        return _scan_op_info(n, dtype, op, exclusive, device)
     info = (ctypes.c_longlong * 4)()
     with torch.cuda.device(torch.device(device)):
         _ext.call_hip("cme_scan32_info", n, _SCAN32_KINDS[kind], _DT_SCAN[dtype], int(exclusive),
@@ -128,14 +169,21 @@ def scan_launch_info(n: int, kind: str = "lookback", exclusive: bool = False, de
 _ext.proto(_ext.HIP_PROTOS, "cme_scan64_info", "qp")
 
 
-def scan64_launch_info(n: int, device: torch.device | str = "cuda") -> dict:
+def scan64_launch_info(n: int, device: torch.device | str = "cuda", op: str = "sum",
+                       dtype: torch.dtype = torch.int64, exclusive: bool = False) -> dict:
     """How the 64-bit scans of ``n`` elements are launched on ``device``:
     ``tile`` (elements), ``tiles``, ``lookback_workgroups`` (the persistent,
     co-resident grid of ``algo="lookback"``), ``rts_chunks`` and
     ``rts_tiles_per_chunk`` (``algo="rts"``, whose tiles are ``rts_tile``
-    elements), ``lookback_ws_bytes``."""
+    elements), ``lookback_ws_bytes``. ``op="max"`` / ``"min"``: the same keys
+    (and ``blocks_per_cu``) for the max / min kernels of ``dtype`` and
+    ``exclusive``."""
     import ctypes
 
+    if op != "sum":
+        d = _scan_op_info(n, dtype, op, exclusive, device)
+        d["lookback_workgroups"] = d.pop("workgroups")
+        return d
     info = (ctypes.c_longlong * 7)()
     with torch.cuda.device(torch.device(device)):
         _ext.call_hip("cme_scan64_info", n, ctypes.addressof(info))
@@ -230,8 +278,10 @@ def _check_lookback(x: torch.Tensor, before: bool = False) -> None:
 
 
 def scan(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = None,
-         algo: str = "auto") -> torch.Tensor:
+         algo: str = "auto", op: str = "sum") -> torch.Tensor:
     """Prefix sum of a 1-D contiguous float32/int32/uint32/int64/float64 tensor.
+    ``op="max"`` / ``"min"``: the running maximum / minimum instead, see
+    :func:`cummax`.
     algo: "auto" ("lookback" for 32-bit integers, whose sums are exact in any
     order; "rts" for float32 and float64, whose fixed summation tree is bitwise
     reproducible -- look-back's float prefixes depend on which predecessor had
@@ -249,6 +299,10 @@ def scan(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = No
     that is not 16-byte aligned is staged through an aligned copy on the GPU
     (the ``_mlevel`` forms take it as it is). ``out`` (same dtype and length,
     contiguous) may be ``x`` itself for "rts" and "lookback"."""
+    if op not in _OPS:
+        raise ValueError(f"scan: op {op!r} is not one of {sorted(_OPS)}")
+    if op != "sum":
+        return _scan_minmax(x, exclusive, out, algo, op)
     if not x.is_contiguous():
         x = x.contiguous()
     if out is not None and (out.dtype != x.dtype or out.numel() != x.numel() or out.device != x.device
@@ -314,6 +368,70 @@ def scan(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = No
         _ext.call_cpu("cme_cpu_scan", x.data_ptr(), out.data_ptr(), n, _DT64[x.dtype] if wide else _DT_SCAN[x.dtype],
                       int(exclusive))
     return out
+
+
+def _scan_minmax(x: torch.Tensor, exclusive: bool, out: torch.Tensor | None, algo: str, op: str) -> torch.Tensor:
+    if x.dtype not in _DT_SCAN and x.dtype not in _DT64:
+        raise TypeError(f"scan: {x.dtype} is not supported")
+    if algo not in ("auto",) + _ALGOS_MINMAX:
+        raise TypeError(f"scan: algo {algo!r} is sum only; op={op!r} takes "
+                        + " or ".join(repr(a) for a in _ALGOS_MINMAX))
+    if not x.is_contiguous():
+        x = x.contiguous()
+    if out is not None and (out.dtype != x.dtype or out.numel() != x.numel() or out.device != x.device
+                            or not out.is_contiguous()):
+        raise ValueError("scan: out must be a contiguous tensor of x's dtype, length and device")
+    out = torch.empty_like(x) if out is None else out
+    if algo == "auto":
+        algo = _AUTO_MINMAX[x.dtype]
+    n = x.numel()
+    wide = x.dtype in _DT64
+    code = _DT64[x.dtype] if wide else _DT_SCAN[x.dtype]
+    if not x.is_cuda:
+        _ext.call_cpu("cme_cpu_scan_op", x.data_ptr(), out.data_ptr(), n, code, _OPS[op], int(exclusive))
+        return out
+    if not wide and (x.data_ptr() % 16 or out.data_ptr() % 16):
+        # a 32-bit view that is only 4-byte aligned: see scan() and _aligned
+        staged = _scan_minmax(_aligned(x), exclusive, out if out.data_ptr() % 16 == 0 else None, algo, op)
+        if staged is not out:
+            out.copy_(staged)
+        return out
+    s = _ext.stream_ptr(x.device)
+    if algo == "lookback":
+        # the descriptors and the epoch count of the sum scans of this width
+        _check_lookback(x, before=True)
+        ws, epoch = _lookback64_ws(x) if wide else _lookback_ws(x)
+        _ext.call_hip("cme_scan_op", x.data_ptr(), out.data_ptr(), n, code, _OPS[op], int(exclusive),
+                      ws.data_ptr(), epoch, s)
+        _check_lookback(x)
+    else:
+        _ext.call_hip("cme_scan_rts_op", x.data_ptr(), out.data_ptr(), n, code, _OPS[op], int(exclusive),
+                      workspace(x.device, 8192, "rts").data_ptr(), s)
+    return out
+
+
+def cummax(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = None,
+           algo: str = "auto") -> torch.Tensor:
+    """Running maximum of a 1-D float32/int32/uint32/int64/float64 tensor:
+    ``out[i] = max(x[0..i])``, the values of ``torch.cummax(x, 0)`` bit for bit
+    (no index output). NaN is sticky -- every output from the first NaN on is
+    NaN -- and among equal values the later element wins, which shows only
+    between ``+0.0`` and ``-0.0``. ``exclusive``: ``out[0]`` is the identity
+    (``-inf``; the type's minimum for integers) and ``out[i]`` the inclusive
+    ``out[i-1]``.
+
+    ``algo``: "lookback" (single pass; also "auto" for every dtype: the
+    operator is exactly associative, so the result does not depend on the order
+    in which workgroups publish) or "rts" (reduce-then-scan); any other raises
+    a ``TypeError``. ``out``, alignment and the CPU backend as :func:`scan`."""
+    return scan(x, exclusive, out, algo, op="max")
+
+
+def cummin(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = None,
+           algo: str = "auto") -> torch.Tensor:
+    """Running minimum: the mirror image of :func:`cummax` (identity ``+inf`` /
+    the type's maximum)."""
+    return scan(x, exclusive, out, algo, op="min")
 
 
 def reduce(x: torch.Tensor, op: str = "sum", algo: str = "vector") -> torch.Tensor:

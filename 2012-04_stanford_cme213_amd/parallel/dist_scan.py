@@ -8,7 +8,7 @@ block (LDS) -> device (decoupled look-back / reduce-then-scan) -> GPUs
 scan-then-add (``my-refs/scan.pdf`` Fig. 5) is the same idea one level down.
 
 * :func:`dist_scan` -- plain (inclusive / exclusive) sum scan of a sharded
-  vector.
+  vector, or its running max / min (``op="max"`` / ``"min"``).
 * :func:`dist_segmented_scan` -- inclusive segmented sum scan with head flags.
   A segment may straddle shards: the carry into rank r is the sum of the
   trailing partial segments of ranks j..r-1, where j is the last rank before
@@ -31,8 +31,52 @@ from ..ops.scan import scan, segmented_scan
 from .comm import Comm
 
 
-def dist_scan(x: torch.Tensor, comm: Comm, exclusive: bool = False) -> torch.Tensor:
-    """Global scan of the concatenation of every rank's shard ``x``."""
+def _identity(op: str, dtype: torch.dtype) -> float | int:
+    """The identity of the max / min scans: -inf / +inf, or the integer type's
+    minimum / maximum."""
+    if dtype.is_floating_point:
+        return float("-inf") if op == "max" else float("inf")
+    if dtype == torch.uint32:
+        return 0 if op == "max" else 0xFFFFFFFF
+    info = torch.iinfo(dtype)
+    return info.min if op == "max" else info.max
+
+
+def _combine(op: str, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """The max / min scans' operator, ``a`` the earlier operand: ``(b >= a ||
+    b != b) ? b : a`` and its mirror image. ``torch.maximum`` would not do: the
+    later of two equal values wins (+0.0 / -0.0) and NaN is sticky. uint32
+    (which torch does not compare) is ordered through int64."""
+    ka, kb = (a.to(torch.int64), b.to(torch.int64)) if a.dtype == torch.uint32 else (a, b)
+    later = (kb >= ka) if op == "max" else (kb <= ka)
+    return torch.where(later | (kb != kb), b, a)
+
+
+def _dist_scan_minmax(x: torch.Tensor, comm: Comm, exclusive: bool, op: str) -> torch.Tensor:
+    ident = torch.full((1,), _identity(op, x.dtype), dtype=x.dtype, device=x.device)
+    if x.numel() == 0:
+        y, total = x.clone(), ident  # an empty shard contributes the identity
+    else:
+        y = scan(x, exclusive=exclusive, op=op)
+        total = _combine(op, y[-1:], x[-1:]) if exclusive else y[-1:].clone()
+    totals = comm.allgather(total).view(-1)
+    carry = ident
+    for r in range(comm.rank):  # the earlier ranks' totals, in rank order
+        carry = _combine(op, carry, totals[r:r + 1])
+    if y.numel():
+        y.copy_(_combine(op, carry.expand_as(y), y))
+    return y
+
+
+def dist_scan(x: torch.Tensor, comm: Comm, exclusive: bool = False, op: str = "sum") -> torch.Tensor:
+    """Global scan of the concatenation of every rank's shard ``x``. ``op``:
+    "sum", or "max" / "min" for the running maximum / minimum
+    (:func:`~cme213x.ops.scan.cummax`): the carry into rank r is the earlier
+    ranks' totals combined in rank order by the scan's own operator."""
+    if op not in ("sum", "max", "min"):
+        raise ValueError(f"dist_scan: op {op!r} is not one of ['max', 'min', 'sum']")
+    if op != "sum":
+        return _dist_scan_minmax(x, comm, exclusive, op)
     if x.numel() == 0:
         y = x.clone()
         total = torch.zeros(1, dtype=x.dtype, device=x.device)

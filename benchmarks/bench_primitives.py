@@ -7,6 +7,9 @@ per measurement with the reference number it is compared against.
   reduce     2^26 elements
   scan64     int64 / float64 scans and sums at 2^25 and 2^27 against the copy
              rate of the same run (profiles/scan64_r8.md)
+  scan_minmax  running max (cummax) by look-back and reduce-then-scan against the
+             sum look-back, torch.cummax and the copy of the same run, float32 /
+             int32 / int64 / float64 at 2^25 and 2^27 (profiles/scan_minmax.md)
   spmvscan   the 15 final-project shapes (BASELINE #19-21, synthetic values)
   cipher     19.76 MB moby-dick x16 (BASELINE #1-3)
   pagerank   2^21 nodes, avg 8 edges, 20 iterations (BASELINE #5)
@@ -105,6 +108,29 @@ def main():
         emit(bench="reduce", algo="torch.sum", n=n, ms=ms, GBps=4 * n / ms / 1e6)
         del x, y, xi, yi
 
+    # The arms of one (dtype, size) alternate call by call in this process (in
+    # an order reshuffled every round); every call of an arm takes the next of
+    # three operand sets. Returns {arm: (median, min, max) ms}.
+    def alternate(arms, rounds=12, warm=2):
+        import random
+
+        order = list(arms)
+        rnd = random.Random(0)
+        ts = {a: [] for a in arms}
+        turn = {a: 0 for a in arms}
+        for r in range(rounds + warm):
+            rnd.shuffle(order)  # no arm always runs behind the same predecessor
+            for name in order:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                arms[name](turn[name] % 3)
+                e1.record()
+                e1.synchronize()
+                turn[name] += 1
+                if r >= warm:
+                    ts[name].append(e0.elapsed_time(e1))
+        return {a: (sorted(t)[len(t) // 2], min(t), max(t)) for a, t in ts.items()}
+
     if want("scan64"):
         # int64 / float64 at 2^25 and 2^27: the arms of one (dtype, size)
         # alternate call by call in this process (in an order reshuffled every
@@ -112,26 +138,6 @@ def main():
         # (cache-defeated: 3 x 16 B x n is far past the 256 MB Infinity Cache at
         # both sizes) and the copy of the same operands is one of the arms, so
         # every share is against the copy rate of the same run.
-        def alternate(arms, rounds=12, warm=2):
-            import random
-
-            order = list(arms)
-            rnd = random.Random(0)
-            ts = {a: [] for a in arms}
-            turn = {a: 0 for a in arms}
-            for r in range(rounds + warm):
-                rnd.shuffle(order)  # no arm always runs behind the same predecessor
-                for name in order:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    arms[name](turn[name] % 3)
-                    e1.record()
-                    e1.synchronize()
-                    turn[name] += 1
-                    if r >= warm:
-                        ts[name].append(e0.elapsed_time(e1))
-            return {a: (sorted(t)[len(t) // 2], min(t), max(t)) for a, t in ts.items()}
-
         for dt in (torch.int64, torch.float64):
             for n in (1 << 25, 1 << 27):
                 if dt == torch.int64:
@@ -154,6 +160,44 @@ def main():
                     emit(bench="scan64", dtype=str(dt).split(".")[1], n=n, arm=name, ms=round(ms, 4),
                          ms_min=round(lo, 4), ms_max=round(hi, 4), model_B_per_elem=per,
                          GBps=round(per * n / ms / 1e6, 1), share_of_copy=round(per * n / ms / 1e6 / copy_bps, 3))
+                sc.check_lookback(dev)
+                del xs, ys, arms
+
+    if want("scan_minmax"):
+        # Running max by both algorithms against the SUM look-back of the same
+        # dtype (the same bytes through the same schedule), torch.cummax (which
+        # also writes an int64 index per element) and the copy of the same
+        # operands; measured like scan64: three cache-defeated operand sets (3 x
+        # 8 B x 2^25 is past the 256 MB Infinity Cache), arms alternated. Noisy
+        # ramps, so the running max changes all along. `ok`: the max look-back
+        # is no slower than the sum look-back by more than the spread (max -
+        # min) the sum arm itself shows in this run.
+        for dt in (torch.float32, torch.int32, torch.int64, torch.float64):
+            for n in (1 << 25, 1 << 27):
+                ramp = torch.arange(n, device=dev, dtype=torch.int64)
+                xs = [(ramp + torch.randint(-50, 51, (n,), device=dev)).to(dt) for _ in range(3)]
+                del ramp
+                ys = [torch.empty_like(x) for x in xs]
+                arms = {
+                    "copy": lambda k: ys[k].copy_(xs[k]),
+                    "max-lookback": lambda k: sc.scan(xs[k], False, ys[k], "lookback", "max"),
+                    "max-rts": lambda k: sc.scan(xs[k], False, ys[k], "rts", "max"),
+                    "sum-lookback": lambda k: sc.scan(xs[k], False, ys[k], "lookback"),
+                    "torch.cummax": lambda k: torch.cummax(xs[k], 0),
+                }
+                res = alternate(arms)
+                size = xs[0].element_size()
+                copy_bps = 2 * size * n / res["copy"][0] / 1e6
+                sum_ms, sum_lo, sum_hi = res["sum-lookback"]
+                for name, (ms, lo, hi) in res.items():
+                    extra = {}
+                    if name == "max-lookback":
+                        extra = dict(sum_ms=round(sum_ms, 4), sum_spread_ms=round(sum_hi - sum_lo, 4),
+                                     ok=bool(ms <= sum_ms + (sum_hi - sum_lo)))
+                    emit(bench="scan_minmax", dtype=str(dt).split(".")[1], n=n, arm=name, ms=round(ms, 4),
+                         ms_min=round(lo, 4), ms_max=round(hi, 4), model_B_per_elem=2 * size,
+                         GBps=round(2 * size * n / ms / 1e6, 1),
+                         share_of_copy=round(2 * size * n / ms / 1e6 / copy_bps, 3), **extra)
                 sc.check_lookback(dev)
                 del xs, ys, arms
 

@@ -4,6 +4,7 @@
 #include <omp.h>
 
 #include <cstdint>
+#include <limits>
 #include <type_traits>
 #include <vector>
 
@@ -38,6 +39,65 @@ void scan_impl(const T* in, T* out, long long n, bool exclusive) {
             }
         }
     }
+}
+
+// Running max / min (torch.cummax / cummin values): a is the earlier operand.
+// NaN is sticky and among equal values the later one wins (+0.0 / -0.0), so
+// the operators are associative but not commutative.
+struct CumMax {
+    template <typename T> T operator()(T a, T b) const { return (b >= a || b != b) ? b : a; }
+    template <typename T> static T identity() {
+        return std::numeric_limits<T>::has_infinity ? -std::numeric_limits<T>::infinity()
+                                                    : std::numeric_limits<T>::lowest();
+    }
+};
+struct CumMin {
+    template <typename T> T operator()(T a, T b) const { return (b <= a || b != b) ? b : a; }
+    template <typename T> static T identity() {
+        return std::numeric_limits<T>::has_infinity ? std::numeric_limits<T>::infinity()
+                                                    : std::numeric_limits<T>::max();
+    }
+};
+
+// The three phases of scan_impl for an operator called as op(earlier, later):
+// per-thread block totals, their serial exclusive scan in block order, the
+// per-thread rescan from the block's carry. out may be in.
+template <typename T, typename Op>
+void scan_op_impl(const T* in, T* out, long long n, bool exclusive, Op op) {
+    const T id = Op::template identity<T>();
+    int nt = omp_get_max_threads();
+    std::vector<T> sums(nt + 1, id);
+#pragma omp parallel num_threads(nt)
+    {
+        int t = omp_get_thread_num();
+        int tn = omp_get_num_threads();
+        long long b = n * t / tn, e = n * (t + 1) / tn;
+        T acc = id;
+        for (long long i = b; i < e; ++i) acc = op(acc, in[i]);
+        sums[t + 1] = acc;
+#pragma omp barrier
+#pragma omp single
+        for (int k = 1; k <= tn; ++k) sums[k] = op(sums[k - 1], sums[k]);
+        T run = sums[t];
+        for (long long i = b; i < e; ++i) {
+            T v = in[i];
+            if (exclusive) {
+                out[i] = run;
+                run = op(run, v);
+            } else {
+                run = op(run, v);
+                out[i] = run;
+            }
+        }
+    }
+}
+
+template <typename T>
+int scan_op_dispatch(const void* in, void* out, long long n, int op, bool exclusive) {
+    if (op == 1) scan_op_impl((const T*)in, (T*)out, n, exclusive, CumMax());
+    else if (op == 2) scan_op_impl((const T*)in, (T*)out, n, exclusive, CumMin());
+    else return 1;
+    return 0;
 }
 
 template <typename T>
@@ -86,6 +146,19 @@ CME_CPU_EXPORT int cme_cpu_scan(const void* in, void* out, long long n, int dtyp
     else if (dtype == 4) scan_impl((const double*)in, (double*)out, n, exclusive);
     else return 1;
     return 0;
+}
+
+// op: 0 sum (cme_cpu_scan), 1 max, 2 min -- the running max / min of
+// torch.cummax / cummin (values only). dtype as cme_cpu_scan; int64 compares as
+// signed.
+CME_CPU_EXPORT int cme_cpu_scan_op(const void* in, void* out, long long n, int dtype, int op, int exclusive) {
+    if (op == 0) return cme_cpu_scan(in, out, n, dtype, exclusive);
+    if (dtype == 0) return scan_op_dispatch<float>(in, out, n, op, exclusive);
+    if (dtype == 1) return scan_op_dispatch<int32_t>(in, out, n, op, exclusive);
+    if (dtype == 2) return scan_op_dispatch<uint32_t>(in, out, n, op, exclusive);
+    if (dtype == 3) return scan_op_dispatch<int64_t>(in, out, n, op, exclusive);
+    if (dtype == 4) return scan_op_dispatch<double>(in, out, n, op, exclusive);
+    return 1;
 }
 
 CME_CPU_EXPORT int cme_cpu_reduce(const void* in, long long n, int dtype, int op, void* out) {

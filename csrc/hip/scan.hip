@@ -110,6 +110,79 @@ CME_EXPORT int cme_scan(const void* in, void* out, long long n, int dtype, int e
     }
 }
 
+// Max / min prefix scans (torch.cummax / cummin values; wave.h OpCumMax /
+// OpCumMin): the production kernels instantiated with the operator. op: 0 sum
+// (cme_scan / cme_scan_rts themselves), 1 max, 2 min; dtype, ws, epoch and
+// the alignment rule as for cme_scan. A max scan shares the descriptor array
+// and the epoch count of the sum scans of its width. int64 (dtype 3) compares
+// as signed.
+#define CME_SCAN_OP_DISPATCH(LAUNCH, ...)                                                        \
+    switch (dtype * 4 + op) {                                                                    \
+        case 1: return LAUNCH<float, OpCumMax>((const float*)in, (float*)out, __VA_ARGS__);       \
+        case 2: return LAUNCH<float, OpCumMin>((const float*)in, (float*)out, __VA_ARGS__);       \
+        case 5: return LAUNCH<int, OpCumMax>((const int*)in, (int*)out, __VA_ARGS__);             \
+        case 6: return LAUNCH<int, OpCumMin>((const int*)in, (int*)out, __VA_ARGS__);             \
+        case 9: return LAUNCH<uint32_t, OpCumMax>((const uint32_t*)in, (uint32_t*)out, __VA_ARGS__);  \
+        case 10: return LAUNCH<uint32_t, OpCumMin>((const uint32_t*)in, (uint32_t*)out, __VA_ARGS__); \
+        default: return (int)hipErrorInvalidValue;                                               \
+    }
+
+CME_EXPORT int cme_scan_op(const void* in, void* out, long long n, int dtype, int op, int exclusive, void* ws,
+                           unsigned epoch, void* stream) {
+    if (op == 0) return cme_scan(in, out, n, dtype, exclusive, ws, epoch, stream);
+    if (op < 0 || op > 2 || dtype < 0 || dtype > 4) return (int)hipErrorInvalidValue;
+    hipStream_t s = as_stream(stream);
+    if (dtype >= 3) return scan64_lookback_op(in, out, n, dtype, op, exclusive, ws, s, epoch);
+    if (!aligned16(in, out)) return (int)hipErrorInvalidValue;
+    CME_SCAN_OP_DISPATCH(launch_scan, n, exclusive, ws, s, epoch)
+}
+
+CME_EXPORT int cme_scan_rts_op(const void* in, void* out, long long n, int dtype, int op, int exclusive, void* ws,
+                               void* stream) {
+    if (op == 0) return cme_scan_rts(in, out, n, dtype, exclusive, ws, stream);
+    if (op < 0 || op > 2 || dtype < 0 || dtype > 4) return (int)hipErrorInvalidValue;
+    hipStream_t s = as_stream(stream);
+    if (dtype >= 3) return scan64_rts_op(in, out, n, dtype, op, exclusive, ws, s);
+    if (!aligned16(in, out)) return (int)hipErrorInvalidValue;
+    CME_SCAN_OP_DISPATCH(launch_rts, n, exclusive, ws, s)
+}
+#undef CME_SCAN_OP_DISPATCH
+
+// How cme_scan_op / cme_scan_rts_op launch n elements of (dtype, op, exclusive)
+// on the current device: the max / min kernels are instantiations of their
+// own, so their co-resident grid may differ from the sum kernels'. info[0]
+// look-back tile (elements), [1] its tiles, [2] look-back workgroups (the
+// persistent grid), [3] blocks per CU, [4] reduce-then-scan chunks, [5] its
+// tiles per chunk, [6] its tile (elements), [7] look-back workspace bytes.
+CME_EXPORT int cme_scan_op_info(long long n, int dtype, int op, int exclusive, long long* info) {
+    if (op < 0 || op > 2 || dtype < 0 || dtype > 4) return (int)hipErrorInvalidValue;
+    if (dtype >= 3) return scan64_op_info(n, dtype, op, exclusive, info);
+    int cap;
+    switch (dtype * 4 + op) {
+        case 0: cap = scan32_grid_cap<float>(exclusive); break;
+        case 1: cap = scan32_grid_cap<float, OpCumMax>(exclusive); break;
+        case 2: cap = scan32_grid_cap<float, OpCumMin>(exclusive); break;
+        case 4: cap = scan32_grid_cap<int>(exclusive); break;
+        case 5: cap = scan32_grid_cap<int, OpCumMax>(exclusive); break;
+        case 6: cap = scan32_grid_cap<int, OpCumMin>(exclusive); break;
+        case 8: cap = scan32_grid_cap<uint32_t>(exclusive); break;
+        case 9: cap = scan32_grid_cap<uint32_t, OpCumMax>(exclusive); break;
+        default: cap = scan32_grid_cap<uint32_t, OpCumMin>(exclusive); break;
+    }
+    const long long tiles = n > 0 ? (n + kLbTile - 1) / kLbTile : 0;
+    long long chunk = kScanTile;
+    const int chunks = n > 0 ? rts_chunks(n, &chunk) : 0;
+    info[0] = kLbTile;
+    info[1] = tiles;
+    info[2] = tiles < cap ? tiles : cap;
+    info[3] = cap / device_cu_count();
+    info[4] = chunks;
+    info[5] = chunk / kScanTile;
+    info[6] = kScanTile;
+    info[7] = (long long)lb2_ws_bytes(tiles);
+    return 0;
+}
+
 // How the 32-bit look-back scans of n elements are launched on the current
 // device, by the launchers' own expressions. kind 0: cme_scan (dtype 0 / 1 / 2,
 // exclusive); kind 1: cme_segscan. info: tile (elements), tiles, workgroups
@@ -285,4 +358,10 @@ CME_REGISTER_KERNEL(scan_lookback_f32, 256,
 CME_REGISTER_KERNEL(scan_rts_reduce_f32, 256, rts_reduce_kernel<float>);
 CME_REGISTER_KERNEL(scan_rts_scan_f32, 256, rts_scan_kernel<float, true>);
 CME_REGISTER_KERNEL(scan_blelloch_rts_f32, 256, tile_tree_scan_kernel<float, true, 0>);
+CME_REGISTER_KERNEL(scan_max_lookback_f32, 256,
+                    scan_lookback_kernel<float, true, kLbRows, true, kLbMode, false, kLbPf, kLbNt, OpCumMax>);
+CME_REGISTER_KERNEL(scan_max_lookback_i32, 256,
+                    scan_lookback_kernel<int, true, kLbRows, true, kLbMode, false, kLbPf, kLbNt, OpCumMax>);
+CME_REGISTER_KERNEL(scan_max_rts_reduce_f32, 256, rts_reduce_kernel<float, OpCumMax>);
+CME_REGISTER_KERNEL(scan_max_rts_scan_f32, 256, rts_scan_kernel<float, true, OpCumMax>);
 CME_REGISTER_KERNEL(segscan_bitmask_fused, 256, segscan_kernel<1, true, 4, false, true>);

@@ -27,6 +27,12 @@ constexpr int kSegScan64Tile = 256 * 2 * kSegScan64Rows;  // 4096 elements, 32 K
 int scan64_lookback(const void* in, void* out, long long n, int dtype, int exclusive, void* ws, hipStream_t s,
                     uint32_t epoch);
 int scan64_rts(const void* in, void* out, long long n, int dtype, int exclusive, void* ws, hipStream_t s);
+// Max / min prefix scans (wave.h OpCumMax / OpCumMin; op 1 max, 2 min): int64
+// compares as long long. scan64_op_info: see cme_scan_op_info (scan.hip).
+int scan64_lookback_op(const void* in, void* out, long long n, int dtype, int op, int exclusive, void* ws,
+                       hipStream_t s, uint32_t epoch);
+int scan64_rts_op(const void* in, void* out, long long n, int dtype, int op, int exclusive, void* ws, hipStream_t s);
+int scan64_op_info(long long n, int dtype, int op, int exclusive, long long* info);
 // op: 0 sum, 1 max, 2 min. part: >= 1024 * 8 bytes.
 int reduce64(const void* in, long long n, int dtype, int op, void* part, void* out, hipStream_t s);
 

@@ -10,8 +10,10 @@
 // in the look-back (8192 elements, 64 KB) and 8 rows in the reduce-then-scan.
 // int64 is summed as unsigned long long, so sums wrap
 // modulo 2^64 (signed overflow would be undefined); max / min compare as long
-// long. The 32-bit family (scan_kernels.h) and its tuned constants are not
-// touched.
+// long, and so do the max / min prefix scans (wave.h OpCumMax / OpCumMin: the
+// same kernels with the operator as a template parameter, called as
+// op(earlier, later)). The 32-bit family (scan_kernels.h) and its tuned
+// constants are not touched.
 #include "scan64.h"
 
 #include "cme213/lookback.h"
@@ -42,9 +44,13 @@ constexpr int kLbRows = kScan64LbRows;
 
 // One wave: lanes l < n inspect predecessor slot base - l of (a, inc); see
 // lookback.h lb2_window (this is its unsegmented form over two-granule slots).
-template <typename T>
+// The lanes hold the predecessors latest first: an ordered operator is folded
+// by its mirror image, and empty slots hold its identity.
+template <typename T, typename Op = OpAdd>
 __device__ __forceinline__ bool lb64_window(uint64_t* a, uint64_t* inc, int base, int n, bool virt0, bool all_agg,
                                             uint32_t epoch, T* sum, T* gsum, unsigned* timeout) {
+    using Fold = typename LatestFirst<Op>::type;
+    const T id = Op::template identity<T>();
     const int lane = lane_id();
     for (unsigned spins = 0;; ++spins) {
         const int idx = base - lane;
@@ -63,15 +69,15 @@ __device__ __forceinline__ bool lb64_window(uint64_t* a, uint64_t* inc, int base
         bool bad = lane < k && lane < n && !virt && !aval;
         if (all_agg) bad = bad || (act && !aval);
         if (!__any(bad)) {
-            const T c = lane < k ? (aval ? lb64_val<T>(va) : T(0))
-                                 : (lane == k && act ? lb64_val<T>(si != 0u ? vi : va) : T(0));
-            *sum = wave_reduce(c);
-            if (all_agg) *gsum = wave_reduce(act ? lb64_val<T>(va) : T(0));
+            const T c = lane < k ? (aval ? lb64_val<T>(va) : id)
+                                 : (lane == k && act ? lb64_val<T>(si != 0u ? vi : va) : id);
+            *sum = wave_reduce<Fold>(c);
+            if (all_agg) *gsum = wave_reduce<Fold>(act ? lb64_val<T>(va) : id);
             return k < kWave;
         }
         if (lb_give_up(spins, timeout, lane)) {
-            *sum = T(0);
-            if (all_agg) *gsum = T(0);
+            *sum = id;
+            if (all_agg) *gsum = id;
             return true;
         }
         __builtin_amdgcn_s_sleep(1);
@@ -80,23 +86,24 @@ __device__ __forceinline__ bool lb64_window(uint64_t* a, uint64_t* inc, int base
 
 // Exclusive prefix of tile `tile` (its aggregate `tot` is already in agg[]);
 // publishes inc[tile], and gagg / ginc for a group's last tile. One wave.
-template <typename T>
+template <typename T, typename Op = OpAdd>
 __device__ T lb64_lookback(Lb64 w, int tile, int tiles, T tot, unsigned* timeout, uint32_t epoch) {
+    const Op op;
     const int lane = lane_id();
     const int g = tile >> 6, j = tile & 63;
     const bool last = j == 63 || tile == tiles - 1;
-    T prefix = T(0), gsum = T(0);
+    T prefix = Op::template identity<T>(), gsum = prefix;
     bool done = false;
-    if (j > 0) done = lb64_window<T>(w.agg, w.inc, tile - 1, j, false, last, epoch, &prefix, &gsum, timeout);
-    if (last && lane == 0) lb64_put(w.gagg + 2 * (long long)g, gsum + tot, epoch);  // unblock later groups first
+    if (j > 0) done = lb64_window<T, Op>(w.agg, w.inc, tile - 1, j, false, last, epoch, &prefix, &gsum, timeout);
+    if (last && lane == 0) lb64_put(w.gagg + 2 * (long long)g, op(gsum, tot), epoch);  // unblock later groups first
     for (int gb = g - 1; !done && gb >= 0; gb -= kWave) {
         T s, gs;
-        done = lb64_window<T>(w.gagg, w.ginc, gb, kWave, true, false, epoch, &s, &gs, timeout);
-        prefix = prefix + s;
+        done = lb64_window<T, Op>(w.gagg, w.ginc, gb, kWave, true, false, epoch, &s, &gs, timeout);
+        prefix = op(s, prefix);  // s: the earlier groups
     }
     if (lane == 0) {
-        lb64_put(w.inc + 2 * (long long)tile, prefix + tot, epoch);
-        if (last) lb64_put(w.ginc + 2 * (long long)g, prefix + tot, epoch);
+        lb64_put(w.inc + 2 * (long long)tile, op(prefix, tot), epoch);
+        if (last) lb64_put(w.ginc + 2 * (long long)g, op(prefix, tot), epoch);
     }
     return prefix;
 }
@@ -105,19 +112,21 @@ __device__ T lb64_lookback(Lb64 w, int tile, int tiles, T tot, unsigned* timeout
 // the serial carry across the rows of one wave; leaves in v the lane-local
 // terms and in ex the per-row exclusive prefix inside the wave. Returns the
 // wave's total.
-template <bool EXCLUSIVE, typename T, int ROWS>
+template <bool EXCLUSIVE, typename Op = OpAdd, typename T, int ROWS>
 __device__ __forceinline__ T wave_tile_scan(Vec2<T> (&v)[ROWS], T (&ex)[ROWS]) {
-    T run = T(0);
+    const Op op;
+    const T id = Op::template identity<T>();
+    T run = id;
 #pragma unroll
     for (int k = 0; k < ROWS; ++k) {
-        const T a = v[k].x, b = a + v[k].y;
+        const T a = v[k].x, b = op(a, v[k].y);
         T wt;
-        const T e = wave_exclusive_scan<OpAdd>(b, &wt);
-        ex[k] = run + e;
-        run = run + wt;
+        const T e = wave_exclusive_scan<Op>(b, &wt);
+        ex[k] = op(run, e);
+        run = op(run, wt);
         if (EXCLUSIVE) {
             v[k].y = a;
-            v[k].x = T(0);
+            v[k].x = id;
         } else {
             v[k].y = b;
         }
@@ -132,9 +141,11 @@ __device__ __forceinline__ T wave_tile_scan(Vec2<T> (&v)[ROWS], T (&ex)[ROWS]) {
 // vn, tile + 2G in vn2) and the output is stored non-temporally, as in the
 // 32-bit production kernel. `in` and `out` are not restrict: out may be in
 // (every lane loads exactly the elements it later stores).
-template <typename T, bool EXCLUSIVE, int ROWS = kLbRows>
+template <typename T, bool EXCLUSIVE, int ROWS = kLbRows, typename Op = OpAdd>
 __global__ __launch_bounds__(kThreads) void scan64_lookback_kernel(const T* in, T* out, long long n, uint64_t* desc,
                                                                    int tiles, unsigned* timeout, uint32_t epoch) {
+    const Op op;
+    const T id = Op::template identity<T>();
     constexpr int kRows = ROWS;
     constexpr int kTile = kThreads * 2 * ROWS;
     constexpr int kWaveElems = kWave * 2 * ROWS;
@@ -148,7 +159,7 @@ __global__ __launch_bounds__(kThreads) void scan64_lookback_kernel(const T* in, 
     auto load_tile = [&](long long tile, Vec2<T>(&dst)[kRows]) {
         const long long b = tile * kTile + wid * kWaveElems + lane * 2;
 #pragma unroll
-        for (int k = 0; k < kRows; ++k) dst[k] = load_v2(in, b + k * kRowElems, n, T(0));
+        for (int k = 0; k < kRows; ++k) dst[k] = load_v2(in, b + k * kRowElems, n, id);
     };
     if ((int)blockIdx.x < tiles) {
         load_tile(blockIdx.x, v);
@@ -156,31 +167,31 @@ __global__ __launch_bounds__(kThreads) void scan64_lookback_kernel(const T* in, 
     }
     for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x, parity ^= 1) {
         T ex[kRows];
-        const T run = wave_tile_scan<EXCLUSIVE>(v, ex);
+        const T run = wave_tile_scan<EXCLUSIVE, Op>(v, ex);
         if (lane == 0) s_wtot[parity][wid] = run;
         lds_bcast_sync();
-        T wpre = T(0), tot = T(0);
+        T wpre = id, tot = id;
 #pragma unroll
         for (int w = 0; w < kWaves; ++w) {
             const T t = s_wtot[parity][w];
-            if (w < wid) wpre = wpre + t;
-            tot = tot + t;
+            if (w < wid) wpre = op(wpre, t);
+            tot = op(tot, t);
         }
         if (wid == 0 && lane == 0) lb64_put(views.agg + 2 * tile, tot, epoch);
         Vec2<T> vn2[kRows];
         const long long pf_tile = tile + 2LL * gridDim.x;
         if (pf_tile < tiles) load_tile(pf_tile, vn2);
         if (wid == 0) {
-            const T pre = lb64_lookback<T>(views, (int)tile, tiles, tot, timeout, epoch);
+            const T pre = lb64_lookback<T, Op>(views, (int)tile, tiles, tot, timeout, epoch);
             if (lane == 0) s_prefix[parity] = pre;
         }
         lds_bcast_sync();
-        const T p = s_prefix[parity] + wpre;
+        const T p = op(s_prefix[parity], wpre);
         const long long base = tile * kTile + wid * kWaveElems + lane * 2;
 #pragma unroll
         for (int k = 0; k < kRows; ++k) {
-            const T q = p + ex[k];
-            store_v2<true>(out, base + k * kRowElems, n, Vec2<T>{q + v[k].x, q + v[k].y});
+            const T q = op(p, ex[k]);
+            store_v2<true>(out, base + k * kRowElems, n, Vec2<T>{op(q, v[k].x), op(q, v[k].y)});
         }
 #pragma unroll
         for (int k = 0; k < kRows; ++k) {
@@ -190,24 +201,24 @@ __global__ __launch_bounds__(kThreads) void scan64_lookback_kernel(const T* in, 
     }
 }
 
-template <typename T, int ROWS>
+template <typename T, int ROWS, typename Op = OpAdd>
 int lookback_grid_cap(int exclusive) {
-    static int bpc_e = persistent_blocks_per_cu(scan64_lookback_kernel<T, true, ROWS>, kThreads);
-    static int bpc_i = persistent_blocks_per_cu(scan64_lookback_kernel<T, false, ROWS>, kThreads);
+    static int bpc_e = persistent_blocks_per_cu(scan64_lookback_kernel<T, true, ROWS, Op>, kThreads);
+    static int bpc_i = persistent_blocks_per_cu(scan64_lookback_kernel<T, false, ROWS, Op>, kThreads);
     return device_cu_count() * (exclusive ? bpc_e : bpc_i);
 }
 
 // epoch 0: zero the descriptors first (one memset node, so a captured graph
 // re-zeroes them at every replay); epoch e > 0: the caller zeroed `ws` once
 // and gives every launch a new epoch.
-template <typename T, int ROWS = kLbRows>
+template <typename T, typename Op = OpAdd, int ROWS = kLbRows>
 int launch_lookback(const T* in, T* out, long long n, int exclusive, void* ws, hipStream_t s, uint32_t epoch) {
     if (n <= 0) return 0;
     constexpr long long kTile = kThreads * 2LL * ROWS;
     const long long nt = (n + kTile - 1) / kTile;
     if (nt >= (1ll << 30)) return (int)hipErrorInvalidValue;
     const int tiles = (int)nt;
-    const int cap = lookback_grid_cap<T, ROWS>(exclusive);
+    const int cap = lookback_grid_cap<T, ROWS, Op>(exclusive);
     const int grid = tiles < cap ? tiles : cap;
     unsigned* timeout = lb_host_timeout();
     if (!timeout) return (int)hipErrorOutOfMemory;
@@ -215,10 +226,10 @@ int launch_lookback(const T* in, T* out, long long n, int exclusive, void* ws, h
     if (epoch >= (1u << 24)) return (int)hipErrorInvalidValue;
     if (epoch == 0) CME_TRY(hipMemsetAsync(ws, 0, lb64_ws_bytes(tiles), s));
     if (exclusive)
-        hipLaunchKernelGGL((scan64_lookback_kernel<T, true, ROWS>), dim3(grid), dim3(kThreads), 0, s, in, out, n,
+        hipLaunchKernelGGL((scan64_lookback_kernel<T, true, ROWS, Op>), dim3(grid), dim3(kThreads), 0, s, in, out, n,
                            desc, tiles, timeout, epoch);
     else
-        hipLaunchKernelGGL((scan64_lookback_kernel<T, false, ROWS>), dim3(grid), dim3(kThreads), 0, s, in, out, n,
+        hipLaunchKernelGGL((scan64_lookback_kernel<T, false, ROWS, Op>), dim3(grid), dim3(kThreads), 0, s, in, out, n,
                            desc, tiles, timeout, epoch);
     CME_LAUNCH_STATUS();
 }
@@ -229,42 +240,74 @@ int launch_lookback(const T* in, T* out, long long n, int exclusive, void* ws, h
 // in a register and the next tile prefetched. 24 B/element of traffic; the
 // summation tree depends on n alone, so float64 results are bitwise
 // reproducible.
-template <typename T>
+// An ordered operator must meet the elements in element order, which the sum's
+// per-thread accumulators do not: there each wave folds a contiguous quarter of
+// the chunk, one wave reduction per 128-element row, and the four wave totals
+// are combined in wave order (scan_kernels.h rts_reduce_kernel).
+template <typename T, typename Op = OpAdd>
 __global__ __launch_bounds__(kThreads) void rts64_reduce_kernel(const T* __restrict__ in, long long n, long long chunk,
                                                                 T* __restrict__ part) {
     __shared__ T lds[kWaves];
+    const Op op;
+    const T id = Op::template identity<T>();
     const long long b0 = (long long)blockIdx.x * chunk;
     const long long b1 = b0 + chunk < n ? b0 + chunk : n;
-    T acc = T(0);
-    // one tile (8 loads of 16 B per lane) in flight per iteration
-    for (long long t0 = b0; t0 < b1; t0 += kTile) {
-        Vec2<T> v[kRows];
+    if constexpr (Op::kOrdered) {
+        const int lane = lane_id();
+        const int wid = threadIdx.x / kWave;
+        const long long quarter = chunk / kWaves;  // chunk: whole tiles of 4096
+        const long long w0 = b0 + wid * quarter;
+        const long long w1 = w0 + quarter < b1 ? w0 + quarter : b1;
+        T run = id;
+        for (long long r0 = w0; r0 < w1; r0 += kWaveElems) {  // 8 rows (loads of 16 B per lane) in flight
+            Vec2<T> v[kRows];
 #pragma unroll
-        for (int k = 0; k < kRows; ++k) v[k] = load_v2(in, t0 + (k * kThreads + (int)threadIdx.x) * 2, b1, T(0));
+            for (int k = 0; k < kRows; ++k) v[k] = load_v2(in, r0 + k * kRowElems + lane * 2, w1, id);
 #pragma unroll
-        for (int k = 0; k < kRows; ++k) acc = acc + (v[k].x + v[k].y);
+            for (int k = 0; k < kRows; ++k) run = op(run, wave_reduce<Op>(op(v[k].x, v[k].y)));
+        }
+        if (lane == 0) lds[wid] = run;
+        lds_bcast_sync();
+        if (threadIdx.x == 0) {
+            T r = lds[0];
+#pragma unroll
+            for (int w = 1; w < kWaves; ++w) r = op(r, lds[w]);
+            part[blockIdx.x] = r;
+        }
+    } else {
+        T acc = id;
+        // one tile (8 loads of 16 B per lane) in flight per iteration
+        for (long long t0 = b0; t0 < b1; t0 += kTile) {
+            Vec2<T> v[kRows];
+#pragma unroll
+            for (int k = 0; k < kRows; ++k) v[k] = load_v2(in, t0 + (k * kThreads + (int)threadIdx.x) * 2, b1, id);
+#pragma unroll
+            for (int k = 0; k < kRows; ++k) acc = op(acc, op(v[k].x, v[k].y));
+        }
+        const T r = block_reduce<kWaves>(acc, lds, op);
+        if (threadIdx.x == 0) part[blockIdx.x] = r;
     }
-    const T r = block_reduce<kWaves>(acc, lds, OpAdd());
-    if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
 // exclusive scan of m <= 1024 partials in place, one block of 1024 threads,
 // one partial per thread: the only LDS is the block scan's 16 wave totals of
 // 8 bytes (the 32-bit kernel's 8192-value staging would be 69.6 KB here and is
 // not needed for at most 1024 values).
-template <typename T>
+template <typename T, typename Op = OpAdd>
 __global__ __launch_bounds__(1024) void rts64_partials_kernel(T* part, int m) {
     __shared__ T lds[16];
     const int t = threadIdx.x;
-    const T v = t < m ? part[t] : T(0);
+    const T v = t < m ? part[t] : Op::template identity<T>();
     T tot;
-    const T e = block_exclusive_scan<16>(v, lds, tot, OpAdd());
+    const T e = block_exclusive_scan<16>(v, lds, tot, Op());
     if (t < m) part[t] = e;
 }
 
-template <typename T, bool EXCLUSIVE>
+template <typename T, bool EXCLUSIVE, typename Op = OpAdd>
 __global__ __launch_bounds__(kThreads) void rts64_scan_kernel(const T* in, T* out, long long n, long long chunk,
                                                               const T* __restrict__ part) {
+    const Op op;
+    const T id = Op::template identity<T>();
     __shared__ T s_wtot[2][kWaves];
     const int lane = lane_id();
     const int wid = threadIdx.x / kWave;
@@ -274,30 +317,31 @@ __global__ __launch_bounds__(kThreads) void rts64_scan_kernel(const T* in, T* ou
     Vec2<T> v[kRows], nv[kRows];
     auto load_tile = [&](long long t0, Vec2<T>(&dst)[kRows]) {
 #pragma unroll
-        for (int k = 0; k < kRows; ++k) dst[k] = load_v2(in, t0 + wid * kWaveElems + k * kRowElems + lane * 2, b1, T(0));
+        for (int k = 0; k < kRows; ++k) dst[k] = load_v2(in, t0 + wid * kWaveElems + k * kRowElems + lane * 2, b1, id);
     };
     if (b0 < b1) load_tile(b0, v);
     int parity = 0;
     for (long long t0 = b0; t0 < b1; t0 += kTile, parity ^= 1) {
         if (t0 + kTile < b1) load_tile(t0 + kTile, nv);
         T ex[kRows];
-        const T run = wave_tile_scan<EXCLUSIVE>(v, ex);
+        const T run = wave_tile_scan<EXCLUSIVE, Op>(v, ex);
         if (lane == 0) s_wtot[parity][wid] = run;
         lds_bcast_sync();
-        T wpre = T(0), tot = T(0);
+        T wpre = id, tot = id;
 #pragma unroll
         for (int w = 0; w < kWaves; ++w) {
             const T t = s_wtot[parity][w];
-            if (w < wid) wpre = wpre + t;
-            tot = tot + t;
+            if (w < wid) wpre = op(wpre, t);
+            tot = op(tot, t);
         }
-        const T p = carry + wpre;
+        const T p = op(carry, wpre);
 #pragma unroll
         for (int k = 0; k < kRows; ++k) {
-            const T q = p + ex[k];
-            store_v2(out, t0 + wid * kWaveElems + k * kRowElems + lane * 2, b1, Vec2<T>{q + v[k].x, q + v[k].y});
+            const T q = op(p, ex[k]);
+            store_v2(out, t0 + wid * kWaveElems + k * kRowElems + lane * 2, b1,
+                     Vec2<T>{op(q, v[k].x), op(q, v[k].y)});
         }
-        carry = carry + tot;
+        carry = op(carry, tot);
 #pragma unroll
         for (int k = 0; k < kRows; ++k) v[k] = nv[k];
     }
@@ -315,18 +359,19 @@ RtsShape rts_shape(long long n) {
     return RtsShape{blocks, chunk};
 }
 
-template <typename T>
+template <typename T, typename Op = OpAdd>
 int launch_rts64(const T* in, T* out, long long n, int exclusive, void* ws, hipStream_t s) {
     if (n <= 0) return 0;
     const RtsShape sh = rts_shape(n);
     T* part = (T*)ws;
-    hipLaunchKernelGGL(rts64_reduce_kernel<T>, dim3(sh.blocks), dim3(kThreads), 0, s, in, n, sh.chunk, part);
-    hipLaunchKernelGGL(rts64_partials_kernel<T>, dim3(1), dim3(1024), 0, s, part, sh.blocks);
+    hipLaunchKernelGGL((rts64_reduce_kernel<T, Op>), dim3(sh.blocks), dim3(kThreads), 0, s, in, n, sh.chunk, part);
+    hipLaunchKernelGGL((rts64_partials_kernel<T, Op>), dim3(1), dim3(1024), 0, s, part, sh.blocks);
     if (exclusive)
-        hipLaunchKernelGGL((rts64_scan_kernel<T, true>), dim3(sh.blocks), dim3(kThreads), 0, s, in, out, n, sh.chunk,
-                           (const T*)part);
+        hipLaunchKernelGGL((rts64_scan_kernel<T, true, Op>), dim3(sh.blocks), dim3(kThreads), 0, s, in, out, n,
+                           sh.chunk, (const T*)part);
     else
-        hipLaunchKernelGGL((rts64_scan_kernel<T, false>), dim3(sh.blocks), dim3(kThreads), 0, s, in, out, n, sh.chunk,
+        hipLaunchKernelGGL((rts64_scan_kernel<T, false, Op>), dim3(sh.blocks), dim3(kThreads), 0, s, in, out, n,
+                           sh.chunk,
                            (const T*)part);
     CME_LAUNCH_STATUS();
 }
@@ -394,6 +439,54 @@ int cme::scan64_rts(const void* in, void* out, long long n, int dtype, int exclu
     return (int)hipErrorInvalidValue;
 }
 
+int cme::scan64_lookback_op(const void* in, void* out, long long n, int dtype, int op, int exclusive, void* ws,
+                            hipStream_t s, uint32_t epoch) {
+    using ll = long long;
+    switch (dtype * 4 + op) {
+        case 13: return launch_lookback<ll, OpCumMax>((const ll*)in, (ll*)out, n, exclusive, ws, s, epoch);
+        case 14: return launch_lookback<ll, OpCumMin>((const ll*)in, (ll*)out, n, exclusive, ws, s, epoch);
+        case 17: return launch_lookback<double, OpCumMax>((const double*)in, (double*)out, n, exclusive, ws, s, epoch);
+        case 18: return launch_lookback<double, OpCumMin>((const double*)in, (double*)out, n, exclusive, ws, s, epoch);
+        default: return (int)hipErrorInvalidValue;
+    }
+}
+
+int cme::scan64_rts_op(const void* in, void* out, long long n, int dtype, int op, int exclusive, void* ws,
+                       hipStream_t s) {
+    using ll = long long;
+    switch (dtype * 4 + op) {
+        case 13: return launch_rts64<ll, OpCumMax>((const ll*)in, (ll*)out, n, exclusive, ws, s);
+        case 14: return launch_rts64<ll, OpCumMin>((const ll*)in, (ll*)out, n, exclusive, ws, s);
+        case 17: return launch_rts64<double, OpCumMax>((const double*)in, (double*)out, n, exclusive, ws, s);
+        case 18: return launch_rts64<double, OpCumMin>((const double*)in, (double*)out, n, exclusive, ws, s);
+        default: return (int)hipErrorInvalidValue;
+    }
+}
+
+int cme::scan64_op_info(long long n, int dtype, int op, int exclusive, long long* info) {
+    int cap;
+    switch (dtype * 4 + op) {
+        case 12: cap = lookback_grid_cap<u64, kLbRows>(exclusive); break;
+        case 13: cap = lookback_grid_cap<long long, kLbRows, OpCumMax>(exclusive); break;
+        case 14: cap = lookback_grid_cap<long long, kLbRows, OpCumMin>(exclusive); break;
+        case 16: cap = lookback_grid_cap<double, kLbRows>(exclusive); break;
+        case 17: cap = lookback_grid_cap<double, kLbRows, OpCumMax>(exclusive); break;
+        case 18: cap = lookback_grid_cap<double, kLbRows, OpCumMin>(exclusive); break;
+        default: return (int)hipErrorInvalidValue;
+    }
+    const long long tiles = n > 0 ? (n + kScan64Tile - 1) / kScan64Tile : 0;
+    const RtsShape sh = rts_shape(n > 0 ? n : 1);
+    info[0] = kScan64Tile;
+    info[1] = tiles;
+    info[2] = tiles < cap ? tiles : cap;
+    info[3] = cap / device_cu_count();
+    info[4] = n > 0 ? sh.blocks : 0;
+    info[5] = sh.chunk / kTile;
+    info[6] = kTile;
+    info[7] = (long long)lb64_ws_bytes(tiles);
+    return 0;
+}
+
 int cme::reduce64(const void* in, long long n, int dtype, int op, void* part, void* out, hipStream_t s) {
     if (n <= 0 || op < 0 || op > 2) return (int)hipErrorInvalidValue;
     if (dtype == 3) {
@@ -434,3 +527,7 @@ CME_REGISTER_KERNEL(scan64_rts_reduce_f64, 256, rts64_reduce_kernel<double>);
 CME_REGISTER_KERNEL(scan64_rts_scan_f64, 256, rts64_scan_kernel<double, true>);
 CME_REGISTER_KERNEL(scan64_rts_scan_i64, 256, rts64_scan_kernel<u64, true>);
 CME_REGISTER_KERNEL(reduce64_sum_f64, 256, reduce64_partial_kernel<double, OpAdd>);
+CME_REGISTER_KERNEL(scan64_max_lookback_i64, 256, scan64_lookback_kernel<long long, true, kLbRows, OpCumMax>);
+CME_REGISTER_KERNEL(scan64_max_lookback_f64, 256, scan64_lookback_kernel<double, true, kLbRows, OpCumMax>);
+CME_REGISTER_KERNEL(scan64_max_rts_scan_i64, 256, rts64_scan_kernel<long long, true, OpCumMax>);
+CME_REGISTER_KERNEL(scan64_max_rts_scan_f64, 256, rts64_scan_kernel<double, true, OpCumMax>);

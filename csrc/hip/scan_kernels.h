@@ -68,11 +68,18 @@ __device__ __forceinline__ void store_v4(T* p, long long i, long long n, const V
 // ------------------------------------------------------------ look-back scan
 // ROWS 16-B vectors per lane (tile = 256 * 4 * ROWS elements). LOOKBACK=false
 // is a timing-only diagnostic arm (tiles scanned independently: wrong result).
+// Op: the scan's operator, called as op(earlier, later) throughout (wave.h
+// OpCumMax / OpCumMin are not commutative); pads, the exclusive scan's first
+// element and an empty prefix are its identity. Only the two-level look-back
+// (LBD = 200) is generic over it.
 template <typename T, bool EXCLUSIVE, int ROWS = 4, bool LOOKBACK = true, int LBD = 1, bool LATE_PF0 = false,
-          int PF = 1, bool NTS = false>
+          int PF = 1, bool NTS = false, typename Op = OpAdd>
 __global__ __launch_bounds__(kScanThreads) void scan_lookback_kernel(const T* __restrict__ in, T* __restrict__ out,
                                                                      long long n, uint64_t* desc, int tiles,
                                                                      unsigned* timeout, uint32_t epoch = 0) {
+    static_assert(!Op::kOrdered || (LOOKBACK && LBD == 200), "max / min scans use the two-level look-back");
+    const Op op;
+    const T id = Op::template identity<T>();
     constexpr int TILE = kScanThreads * 4 * ROWS;
     constexpr int WAVE_ELEMS = kWave * 4 * ROWS;
     __shared__ T s_wtot[2][kScanWaves];
@@ -92,12 +99,12 @@ __global__ __launch_bounds__(kScanThreads) void scan_lookback_kernel(const T* __
     if (blockIdx.x < tiles) {
         const long long b0 = (long long)blockIdx.x * TILE + wid * WAVE_ELEMS;
 #pragma unroll
-        for (int k = 0; k < ROWS; ++k) v[k] = load_v4(in, b0 + k * 256 + lane * 4, n, T(0));
+        for (int k = 0; k < ROWS; ++k) v[k] = load_v4(in, b0 + k * 256 + lane * 4, n, id);
         if constexpr (PF == 2) {
             const long long b1 = (long long)(blockIdx.x + gridDim.x) * TILE + wid * WAVE_ELEMS;
             if (blockIdx.x + gridDim.x < tiles) {
 #pragma unroll
-                for (int k = 0; k < ROWS; ++k) vn[k] = load_v4(in, b1 + k * 256 + lane * 4, n, T(0));
+                for (int k = 0; k < ROWS; ++k) vn[k] = load_v4(in, b1 + k * 256 + lane * 4, n, id);
             }
         }
     }
@@ -106,20 +113,20 @@ __global__ __launch_bounds__(kScanThreads) void scan_lookback_kernel(const T* __
 
     // in-lane inclusive scan of each 4-vector, wave scans of the lane totals,
     // serial carry across the wave-rows
-    T run = T(0);
+    T run = id;
     T ex[ROWS];
 #pragma unroll
     for (int k = 0; k < ROWS; ++k) {
-        T a = v[k].x, b = a + v[k].y, c = b + v[k].z, d = c + v[k].w;
+        T a = v[k].x, b = op(a, v[k].y), c = op(b, v[k].z), d = op(c, v[k].w);
         T wt;
-        T e = wave_exclusive_scan<OpAdd>(d, &wt);
-        ex[k] = run + e;
-        run = run + wt;
+        T e = wave_exclusive_scan<Op>(d, &wt);
+        ex[k] = op(run, e);
+        run = op(run, wt);
         if (EXCLUSIVE) {
             v[k].w = c;
             v[k].z = b;
             v[k].y = a;
-            v[k].x = T(0);
+            v[k].x = id;
         } else {
             v[k].y = b;
             v[k].z = c;
@@ -128,12 +135,12 @@ __global__ __launch_bounds__(kScanThreads) void scan_lookback_kernel(const T* __
     }
     if (lane == 0) s_wtot[parity][wid] = run;
     lds_bcast_sync();
-    T wpre = T(0), tot = T(0);
+    T wpre = id, tot = id;
 #pragma unroll
     for (int w = 0; w < kScanWaves; ++w) {
         T t = s_wtot[parity][w];
-        if (w < wid) wpre = wpre + t;
-        tot = tot + t;
+        if (w < wid) wpre = op(wpre, t);
+        tot = op(tot, t);
     }
     constexpr bool kTwoLevel = LBD == 200;
     if constexpr (kTwoLevel) {
@@ -154,15 +161,15 @@ __global__ __launch_bounds__(kScanThreads) void scan_lookback_kernel(const T* __
 #pragma unroll
         for (int k = 0; k < ROWS; ++k) {
             if constexpr (PF == 2)
-                vn2[k] = load_v4(in, nb + k * 256 + lane * 4, n, T(0));
+                vn2[k] = load_v4(in, nb + k * 256 + lane * 4, n, id);
             else
-                vn[k] = load_v4(in, nb + k * 256 + lane * 4, n, T(0));
+                vn[k] = load_v4(in, nb + k * 256 + lane * 4, n, id);
         }
     }
     if (!LOOKBACK) {
         if (threadIdx.x == 0) s_prefix[parity] = T(0);
     } else if (kTwoLevel && wid == 0) {
-        const T pre = lb2_lookback<T>(lb2_views(desc, tiles), tile, tiles, tot, 0u, timeout, epoch);
+        const T pre = lb2_lookback<T, false, Op>(lb2_views(desc, tiles), tile, tiles, tot, 0u, timeout, epoch);
         if (lane == 0) s_prefix[parity] = pre;
     } else if (wid == 0) {
         if (tile == 0) {
@@ -189,11 +196,11 @@ __global__ __launch_bounds__(kScanThreads) void scan_lookback_kernel(const T* __
         }
     }
     lds_bcast_sync();
-    const T p = s_prefix[parity] + wpre;
+    const T p = op(s_prefix[parity], wpre);
 #pragma unroll
     for (int k = 0; k < ROWS; ++k) {
-        const T q = p + ex[k];
-        Vec4<T> r{q + v[k].x, q + v[k].y, q + v[k].z, q + v[k].w};
+        const T q = op(p, ex[k]);
+        Vec4<T> r{op(q, v[k].x), op(q, v[k].y), op(q, v[k].z), op(q, v[k].w)};
         const long long oi = base + k * 256 + lane * 4;
         if (NTS && oi + 3 < n) {  // write-once output: stream it past the caches
             typedef T v4 __attribute__((ext_vector_type(4)));
@@ -220,19 +227,46 @@ __global__ __launch_bounds__(kScanThreads) void scan_lookback_kernel(const T* __
 // bitwise reproducible (fixed summation tree).
 constexpr int kRtsBlocks = 1024;
 
-template <typename T>
+// An ordered operator (wave.h OpCumMax / OpCumMin) must meet the chunk's
+// elements in element order, which the per-thread accumulators of the sum
+// (each over every 256th vector) do not: there each wave folds a contiguous
+// quarter of the chunk, one wave reduction per 256-element row, four rows of
+// loads in flight, and the four wave totals are combined in wave order.
+template <typename T, typename Op = OpAdd>
 __global__ __launch_bounds__(256) void rts_reduce_kernel(const T* __restrict__ in, long long n, long long chunk,
                                                          T* __restrict__ part) {
     __shared__ T lds[4];
+    const Op op;
+    const T id = Op::template identity<T>();
     const long long b0 = (long long)blockIdx.x * chunk;
     const long long b1 = b0 + chunk < n ? b0 + chunk : n;
-    T acc = T(0);
-    for (long long i = b0 + threadIdx.x * 4; i < b1; i += 1024) {
-        Vec4<T> v = load_v4(in, i, b1, T(0));
-        acc = acc + ((v.x + v.y) + (v.z + v.w));
+    if constexpr (Op::kOrdered) {
+        const int lane = lane_id();
+        const int wid = threadIdx.x / kWave;
+        const long long quarter = chunk / 4;  // chunk: whole 4096-element tiles
+        const long long w0 = b0 + wid * quarter;
+        const long long w1 = w0 + quarter < b1 ? w0 + quarter : b1;
+        T run = id;
+        for (long long i = w0 + lane * 4; i - lane * 4 < w1; i += 1024) {
+            Vec4<T> v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = load_v4(in, i + k * 256, w1, id);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                run = op(run, wave_reduce<Op>(op(op(op(v[k].x, v[k].y), v[k].z), v[k].w)));
+        }
+        if (lane == 0) lds[wid] = run;
+        lds_bcast_sync();
+        if (threadIdx.x == 0) part[blockIdx.x] = op(op(op(lds[0], lds[1]), lds[2]), lds[3]);
+    } else {
+        T acc = id;
+        for (long long i = b0 + threadIdx.x * 4; i < b1; i += 1024) {
+            Vec4<T> v = load_v4(in, i, b1, id);
+            acc = op(acc, op(op(v.x, v.y), op(v.z, v.w)));
+        }
+        T r = block_reduce<4>(acc, lds, op);
+        if (threadIdx.x == 0) part[blockIdx.x] = r;
     }
-    T r = block_reduce<4>(acc, lds, OpAdd());
-    if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
 // exclusive scan of m partials in place, one block of 1024 threads: 8192
@@ -240,19 +274,21 @@ __global__ __launch_bounds__(256) void rts_reduce_kernel(const T* __restrict__ i
 // 8 consecutive values per thread scanned serially, the 1024 thread totals by
 // the block scan (m = 16384 tile sums of a 2^26 tree scan: 2 rounds; direct
 // thread-contiguous global loads touched 16x the lines and took 17 us)
-template <typename T>
+template <typename T, typename Op = OpAdd>
 __global__ __launch_bounds__(1024) void rts_partials_kernel(T* part, int m) {
+    const Op op;
+    const T id = Op::template identity<T>();
     constexpr int kPer = 8, kRound = 1024 * kPer;
     __shared__ T lds[16];
     __shared__ T stage[kRound + kRound / 16];  // one pad word per 16 (thread runs of 8: conflict-free halves)
     auto sp = [](int i) { return i + (i >> 4); };
     const int t = threadIdx.x;
-    T carry = T(0);
+    T carry = id;
     for (int base = 0; base < m; base += kRound) {
 #pragma unroll
         for (int k = 0; k < kPer / 4; ++k) {
             const int e = (k * 1024 + t) * 4;
-            const Vec4<T> q = load_v4(part, (long long)base + e, m, T(0));
+            const Vec4<T> q = load_v4(part, (long long)base + e, m, id);
             stage[sp(e)] = q.x;
             stage[sp(e + 1)] = q.y;
             stage[sp(e + 2)] = q.z;
@@ -260,18 +296,18 @@ __global__ __launch_bounds__(1024) void rts_partials_kernel(T* part, int m) {
         }
         __syncthreads();
         T v[kPer];
-        T acc = T(0);
+        T acc = id;
 #pragma unroll
         for (int k = 0; k < kPer; ++k) {
             v[k] = stage[sp(t * kPer + k)];
-            acc = acc + v[k];
+            acc = op(acc, v[k]);
         }
         T tot;
-        T run = carry + block_exclusive_scan<16>(acc, lds, tot, OpAdd());  // (its barriers order the reads)
+        T run = op(carry, block_exclusive_scan<16>(acc, lds, tot, op));  // (its barriers order the reads)
 #pragma unroll
         for (int k = 0; k < kPer; ++k) {
             stage[sp(t * kPer + k)] = run;
-            run = run + v[k];
+            run = op(run, v[k]);
         }
         __syncthreads();
 #pragma unroll
@@ -280,14 +316,16 @@ __global__ __launch_bounds__(1024) void rts_partials_kernel(T* part, int m) {
             store_v4(part, (long long)base + e, m, Vec4<T>{stage[sp(e)], stage[sp(e + 1)], stage[sp(e + 2)], stage[sp(e + 3)]});
         }
         __syncthreads();  // the next round's staging writes
-        carry = carry + tot;
+        carry = op(carry, tot);
     }
 }
 
-template <typename T, bool EXCLUSIVE>
+template <typename T, bool EXCLUSIVE, typename Op = OpAdd>
 __global__ __launch_bounds__(256) void rts_scan_kernel(const T* __restrict__ in, T* __restrict__ out, long long n,
                                                        long long chunk, const T* __restrict__ part) {
     __shared__ T s_wtot[2][kScanWaves];
+    const Op op;
+    const T id = Op::template identity<T>();
     const int lane = lane_id();
     const int wid = threadIdx.x / kWave;
     const long long b0 = (long long)blockIdx.x * chunk;
@@ -296,26 +334,26 @@ __global__ __launch_bounds__(256) void rts_scan_kernel(const T* __restrict__ in,
     Vec4<T> v[4], nv[4];
     auto load_tile = [&](long long t0, Vec4<T>* dst) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k] = load_v4(in, t0 + wid * 1024 + k * 256 + lane * 4, b1, T(0));
+        for (int k = 0; k < 4; ++k) dst[k] = load_v4(in, t0 + wid * 1024 + k * 256 + lane * 4, b1, id);
     };
     if (b0 < b1) load_tile(b0, v);
     int parity = 0;
     for (long long t0 = b0; t0 < b1; t0 += kScanTile, parity ^= 1) {
         if (t0 + kScanTile < b1) load_tile(t0 + kScanTile, nv);
-        T run = T(0);
+        T run = id;
         T ex[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            T a = v[k].x, b = a + v[k].y, c = b + v[k].z, d = c + v[k].w;
+            T a = v[k].x, b = op(a, v[k].y), c = op(b, v[k].z), d = op(c, v[k].w);
             T wt;
-            T e = wave_exclusive_scan<OpAdd>(d, &wt);
-            ex[k] = run + e;
-            run = run + wt;
+            T e = wave_exclusive_scan<Op>(d, &wt);
+            ex[k] = op(run, e);
+            run = op(run, wt);
             if (EXCLUSIVE) {
                 v[k].w = c;
                 v[k].z = b;
                 v[k].y = a;
-                v[k].x = T(0);
+                v[k].x = id;
             } else {
                 v[k].y = b;
                 v[k].z = c;
@@ -324,40 +362,47 @@ __global__ __launch_bounds__(256) void rts_scan_kernel(const T* __restrict__ in,
         }
         if (lane == 0) s_wtot[parity][wid] = run;
         lds_bcast_sync();
-        T wpre = T(0), tot = T(0);
+        T wpre = id, tot = id;
 #pragma unroll
         for (int w = 0; w < kScanWaves; ++w) {
             T t = s_wtot[parity][w];
-            if (w < wid) wpre = wpre + t;
-            tot = tot + t;
+            if (w < wid) wpre = op(wpre, t);
+            tot = op(tot, t);
         }
-        const T p = carry + wpre;
+        const T p = op(carry, wpre);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const T q = p + ex[k];
-            Vec4<T> r{q + v[k].x, q + v[k].y, q + v[k].z, q + v[k].w};
+            const T q = op(p, ex[k]);
+            Vec4<T> r{op(q, v[k].x), op(q, v[k].y), op(q, v[k].z), op(q, v[k].w)};
             store_v4(out, t0 + wid * 1024 + k * 256 + lane * 4, b1, r);
         }
-        carry = carry + tot;
+        carry = op(carry, tot);
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = nv[k];
     }
 }
 
-template <typename T>
-int launch_rts(const T* in, T* out, long long n, int exclusive, void* ws, hipStream_t s) {
-    if (n <= 0) return 0;
+// chunks (= workgroups = partials) of the reduce-then-scan and the elements of
+// each: whole tiles
+inline int rts_chunks(long long n, long long* chunk) {
     long long tiles = (n + kScanTile - 1) / kScanTile;
     int blocks = tiles < kRtsBlocks ? (int)tiles : kRtsBlocks;
-    long long chunk = ((tiles + blocks - 1) / blocks) * kScanTile;
-    blocks = (int)((n + chunk - 1) / chunk);
+    *chunk = ((tiles + blocks - 1) / blocks) * kScanTile;
+    return (int)((n + *chunk - 1) / *chunk);
+}
+
+template <typename T, typename Op = OpAdd>
+int launch_rts(const T* in, T* out, long long n, int exclusive, void* ws, hipStream_t s) {
+    if (n <= 0) return 0;
+    long long chunk;
+    const int blocks = rts_chunks(n, &chunk);
     T* part = (T*)ws;
-    hipLaunchKernelGGL(rts_reduce_kernel<T>, dim3(blocks), dim3(256), 0, s, in, n, chunk, part);
-    hipLaunchKernelGGL(rts_partials_kernel<T>, dim3(1), dim3(1024), 0, s, part, blocks);
+    hipLaunchKernelGGL((rts_reduce_kernel<T, Op>), dim3(blocks), dim3(256), 0, s, in, n, chunk, part);
+    hipLaunchKernelGGL((rts_partials_kernel<T, Op>), dim3(1), dim3(1024), 0, s, part, blocks);
     if (exclusive)
-        hipLaunchKernelGGL((rts_scan_kernel<T, true>), dim3(blocks), dim3(256), 0, s, in, out, n, chunk, part);
+        hipLaunchKernelGGL((rts_scan_kernel<T, true, Op>), dim3(blocks), dim3(256), 0, s, in, out, n, chunk, part);
     else
-        hipLaunchKernelGGL((rts_scan_kernel<T, false>), dim3(blocks), dim3(256), 0, s, in, out, n, chunk, part);
+        hipLaunchKernelGGL((rts_scan_kernel<T, false, Op>), dim3(blocks), dim3(256), 0, s, in, out, n, chunk, part);
     CME_LAUNCH_STATUS();
 }
 
@@ -952,20 +997,20 @@ constexpr long long kLbTile = 1024LL * kLbRows;  // elements per tile of the pro
 
 // Largest co-resident grid of the production look-back scan (launch_scan and
 // the cme_scan32_info query).
-template <typename T>
+template <typename T, typename Op = OpAdd>
 int scan32_grid_cap(int exclusive) {
     static int bpc_e = persistent_blocks_per_cu(
-        scan_lookback_kernel<T, true, kLbRows, true, kLbMode, false, kLbPf, kLbNt>, kScanThreads);
+        scan_lookback_kernel<T, true, kLbRows, true, kLbMode, false, kLbPf, kLbNt, Op>, kScanThreads);
     static int bpc_i = persistent_blocks_per_cu(
-        scan_lookback_kernel<T, false, kLbRows, true, kLbMode, false, kLbPf, kLbNt>, kScanThreads);
+        scan_lookback_kernel<T, false, kLbRows, true, kLbMode, false, kLbPf, kLbNt, Op>, kScanThreads);
     return device_cu_count() * (exclusive ? bpc_e : bpc_i);
 }
 
-template <typename T>
+template <typename T, typename Op = OpAdd>
 int launch_scan(const T* in, T* out, long long n, int exclusive, void* ws, hipStream_t s, uint32_t epoch) {
     if (n <= 0) return 0;
     const int tiles = (int)((n + kLbTile - 1) / kLbTile);
-    const int cap = scan32_grid_cap<T>(exclusive);
+    const int cap = scan32_grid_cap<T, Op>(exclusive);
     const int grid = tiles < cap ? tiles : cap;
     unsigned* timeout = lb_host_timeout();
     if (!timeout) return (int)hipErrorOutOfMemory;
@@ -973,10 +1018,10 @@ int launch_scan(const T* in, T* out, long long n, int exclusive, void* ws, hipSt
     if (epoch == 0) CME_TRY(hipMemsetAsync(ws, 0, lb2_ws_bytes(tiles), s));
     if (epoch >= (1u << 24)) return (int)hipErrorInvalidValue;
     if (exclusive)
-        hipLaunchKernelGGL((scan_lookback_kernel<T, true, kLbRows, true, kLbMode, false, kLbPf, kLbNt>), dim3(grid),
+        hipLaunchKernelGGL((scan_lookback_kernel<T, true, kLbRows, true, kLbMode, false, kLbPf, kLbNt, Op>), dim3(grid),
                            dim3(kScanThreads), 0, s, in, out, n, desc, tiles, timeout, epoch);
     else
-        hipLaunchKernelGGL((scan_lookback_kernel<T, false, kLbRows, true, kLbMode, false, kLbPf, kLbNt>), dim3(grid),
+        hipLaunchKernelGGL((scan_lookback_kernel<T, false, kLbRows, true, kLbMode, false, kLbPf, kLbNt, Op>), dim3(grid),
                            dim3(kScanThreads), 0, s, in, out, n, desc, tiles, timeout, epoch);
     CME_LAUNCH_STATUS();
 }

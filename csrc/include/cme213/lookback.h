@@ -211,10 +211,19 @@ __device__ __forceinline__ uint32_t lb2_status(uint64_t d, uint32_t epoch) {
 // an inclusive 0 (the start of the array). `all_agg`: additionally require
 // EVERY lane's aggregate and fold them all into (*gsum, *gflag) -- the group's
 // last tile builds gagg from them.
-template <typename T, bool SEG>
+//
+// `Op` (unsegmented walks only): the scan's operator. A window's lanes hold
+// the predecessors NEAREST first, i.e. latest first in element order, so an
+// ordered operator (wave.h OpCumMax / OpCumMin) is folded across the lanes by
+// its mirror image (LatestFirst), and slots that contribute nothing -- the
+// virtual "tile -1" included -- hold the operator's identity.
+template <typename T, bool SEG, typename Op = OpAdd>
 __device__ __forceinline__ bool lb2_window(const uint64_t* a, const uint64_t* inc, int base, int n, bool virt0,
                                            bool all_agg, uint32_t epoch, T* sum, T* gsum, uint32_t* gflag,
                                            unsigned* timeout) {
+    static_assert(!SEG || !Op::kOrdered, "the segmented walk folds sums only");
+    using Fold = typename LatestFirst<Op>::type;
+    const T id = Op::template identity<T>();
     const int lane = lane_id();
     for (unsigned spins = 0;; ++spins) {
         const int idx = base - lane;
@@ -234,21 +243,21 @@ __device__ __forceinline__ bool lb2_window(const uint64_t* a, const uint64_t* in
         if (!__any(bad)) {
             // lane k contributes its inclusive value (or its flagged aggregate)
             const bool use_inc = lane == k && act && si != 0u;
-            const T c = lane < k ? (aval ? lb_val<T>(da) : T(0)) : (lane == k && act ? lb_val<T>(use_inc ? di : da) : T(0));
-            *sum = wave_reduce(c);
+            const T c = lane < k ? (aval ? lb_val<T>(da) : id) : (lane == k && act ? lb_val<T>(use_inc ? di : da) : id);
+            *sum = wave_reduce<Fold>(c);
             if (all_agg) {
                 // ordered segmented fold of every aggregate (nearest first):
                 // stop at the nearest flagged one
                 const uint64_t fm = SEG ? __ballot(aflag) : 0ull;
                 const int kf = fm ? __builtin_ctzll(fm) : kWave;
-                *gsum = wave_reduce(act && lane <= kf ? lb_val<T>(da) : T(0));
+                *gsum = wave_reduce<Fold>(act && lane <= kf ? lb_val<T>(da) : id);
                 *gflag = kf < kWave ? 1u : 0u;
             }
             return k < kWave;
         }
         if (lb_give_up(spins, timeout, lane)) {
-            *sum = T(0);
-            if (all_agg) *gsum = T(0), *gflag = 0u;
+            *sum = id;
+            if (all_agg) *gsum = id, *gflag = 0u;
             return true;
         }
         __builtin_amdgcn_s_sleep(1);
@@ -259,28 +268,30 @@ __device__ __forceinline__ bool lb2_window(const uint64_t* a, const uint64_t* in
 // agg[]); publishes inc[tile] (and gagg / ginc for a group's last tile). For
 // SEGMENTED the returned prefix is the running value entering the tile (the
 // caller ignores it past the tile's first head). One wave.
-template <typename T, bool SEG = false>
+template <typename T, bool SEG = false, typename Op = OpAdd>
 __device__ T lb2_lookback(Lb2 w, int tile, int tiles, T tot, uint32_t tot_flag, unsigned* timeout,
                           uint32_t epoch = 0) {
+    const Op op;
     const int lane = lane_id();
     const int g = tile >> 6, j = tile & 63;
     const bool last = j == 63 || tile == tiles - 1;
-    T prefix = T(0), gsum = T(0);
+    T prefix = Op::template identity<T>(), gsum = prefix;
     uint32_t gflag = 0u;
     bool done = false;
-    if (j > 0) done = lb2_window<T, SEG>(w.agg, w.inc, tile - 1, j, false, last, epoch, &prefix, &gsum, &gflag, timeout);
+    if (j > 0)
+        done = lb2_window<T, SEG, Op>(w.agg, w.inc, tile - 1, j, false, last, epoch, &prefix, &gsum, &gflag, timeout);
     if (last && lane == 0) {  // unblock later groups before walking on
-        const T gv = tot_flag ? tot : gsum + tot;
+        const T gv = tot_flag ? tot : op(gsum, tot);
         lb2_put(w.gagg + g, gv, (tot_flag | gflag) ? kStFlag : 0u, epoch);
     }
     for (int gb = g - 1; !done && gb >= 0; gb -= kWave) {
         T s, gs;
         uint32_t gf;
-        done = lb2_window<T, SEG>(w.gagg, w.ginc, gb, kWave, true, false, epoch, &s, &gs, &gf, timeout);
-        prefix = prefix + s;
+        done = lb2_window<T, SEG, Op>(w.gagg, w.ginc, gb, kWave, true, false, epoch, &s, &gs, &gf, timeout);
+        prefix = op(s, prefix);  // s: the earlier groups
     }
     if (lane == 0) {
-        const T incl = tot_flag ? tot : prefix + tot;
+        const T incl = tot_flag ? tot : op(prefix, tot);
         const uint32_t fl = tot_flag ? kStFlag : 0u;  // informational only: inc always terminates a walk
         lb2_put(w.inc + tile, incl, fl, epoch);
         if (last) lb2_put(w.ginc + g, incl, fl, epoch);

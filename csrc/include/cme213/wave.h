@@ -89,11 +89,15 @@ __device__ __forceinline__ T dpp_move(T old, T src) {
     }
 }
 
+// kOrdered: the functor is not commutative and must be called as
+// op(earlier, later) in element order (see OpCumMax below).
 struct OpAdd {
+    static constexpr bool kOrdered = false;
     template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
     template <typename T> __device__ __forceinline__ static T identity() { return T(0); }
 };
 struct OpMax {
+    static constexpr bool kOrdered = false;
     template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a > b ? a : b; }
     template <typename T> __device__ __forceinline__ static T identity();
 };
@@ -103,6 +107,7 @@ template <> __device__ __forceinline__ int OpMax::identity<int>() { return (int)
 template <> __device__ __forceinline__ uint32_t OpMax::identity<uint32_t>() { return 0u; }
 template <> __device__ __forceinline__ long long OpMax::identity<long long>() { return (long long)(1ull << 63); }
 struct OpMin {
+    static constexpr bool kOrdered = false;
     template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return a < b ? a : b; }
     template <typename T> __device__ __forceinline__ static T identity();
 };
@@ -112,16 +117,55 @@ template <> __device__ __forceinline__ int OpMin::identity<int>() { return 0x7ff
 template <> __device__ __forceinline__ uint32_t OpMin::identity<uint32_t>() { return 0xffffffffu; }
 template <> __device__ __forceinline__ long long OpMin::identity<long long>() { return 0x7fffffffffffffffll; }
 
+// Running max / min of the prefix scans (torch.cummax / cummin values): a is
+// the EARLIER operand, b the later. NaN is sticky, and among equal values the
+// later one wins, which shows only between +0.0 and -0.0. Associative, with
+// the two-sided identity of OpMax / OpMin, but NOT commutative: every caller
+// passes (earlier, later), and a place that holds its operands latest-first
+// (the look-back windows) reduces with OpRev<Op>. reduce keeps OpMax / OpMin,
+// which drop NaN.
+struct OpCumMax {
+    static constexpr bool kOrdered = true;
+    template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return (b >= a || b != b) ? b : a; }
+    template <typename T> __device__ __forceinline__ static T identity() { return OpMax::identity<T>(); }
+};
+struct OpCumMin {
+    static constexpr bool kOrdered = true;
+    template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return (b <= a || b != b) ? b : a; }
+    template <typename T> __device__ __forceinline__ static T identity() { return OpMin::identity<T>(); }
+};
+template <typename Op>
+struct OpRev {
+    static constexpr bool kOrdered = true;
+    template <typename T> __device__ __forceinline__ T operator()(T a, T b) const { return Op()(b, a); }
+    template <typename T> __device__ __forceinline__ static T identity() { return Op::template identity<T>(); }
+};
+// The functor that folds values held latest-first in lane order (Op itself
+// when the order does not matter, so the sum kernels are what they were).
+template <typename Op, bool = Op::kOrdered>
+struct LatestFirst { using type = Op; };
+template <typename Op>
+struct LatestFirst<Op, true> { using type = OpRev<Op>; };
+
+// One step of a wave scan: `v` is this lane's value, `s` came from EARLIER
+// lanes. The commutative functors keep the (v, s) operand order they always
+// had (reduce's OpMax / OpMin NaN behaviour follows from it).
+template <typename Op, typename T>
+__device__ __forceinline__ T wave_step(Op op, T v, T s) {
+    if constexpr (Op::kOrdered) return op(s, v);
+    else return op(v, s);
+}
+
 // Inclusive scan across the 64 lanes of a wave (all lanes must be active).
 template <typename Op = OpAdd, typename T>
 __device__ __forceinline__ T wave_inclusive_scan(T v, Op op = Op()) {
     const T id = Op::template identity<T>();
-    v = op(v, dpp_move<kDppRowShr1>(id, v));
-    v = op(v, dpp_move<kDppRowShr2>(id, v));
-    v = op(v, dpp_move<kDppRowShr4>(id, v));
-    v = op(v, dpp_move<kDppRowShr8>(id, v));
-    v = op(v, dpp_move<kDppRowBcast15, 0xa>(id, v));
-    v = op(v, dpp_move<kDppRowBcast31, 0xc>(id, v));
+    v = wave_step(op, v, dpp_move<kDppRowShr1>(id, v));
+    v = wave_step(op, v, dpp_move<kDppRowShr2>(id, v));
+    v = wave_step(op, v, dpp_move<kDppRowShr4>(id, v));
+    v = wave_step(op, v, dpp_move<kDppRowShr8>(id, v));
+    v = wave_step(op, v, dpp_move<kDppRowBcast15, 0xa>(id, v));
+    v = wave_step(op, v, dpp_move<kDppRowBcast31, 0xc>(id, v));
     return v;
 }
 
