@@ -15,6 +15,7 @@ Ops (schema in each docstring; "!" = mutated in place):
 ``heat_stepn``            nsteps (2-4) timesteps in one HBM pass (temporal blocking)
 ``scan``                  inclusive / exclusive prefix sum
 ``scan_op``               inclusive / exclusive prefix sum / running max / running min
+``scan_dim``              the same along one dimension of a tensor of any rank
 ``segmented_scan``        inclusive segmented sum scan (uint8 heads or int32 bitmask)
 ``sort`` / ``sort_by_key`` stable LSD radix sort, 32- and 64-bit keys (+ 4- / 8-byte values)
 ``argsort``               int64 stable sorting permutation (ascending or descending)
@@ -99,6 +100,17 @@ def scan_op(x: Tensor, op: str, exclusive: bool = False) -> Tensor:
 
 @scan_op.register_fake
 def _(x, op, exclusive=False):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op(f"{NS}::scan_dim", mutates_args=())
+def scan_dim(x: Tensor, dim: int, op: str, exclusive: bool = False) -> Tensor:
+    """scan_dim(Tensor x, int dim, str op, bool exclusive) -> Tensor   (a tensor of any rank along ``dim``)"""
+    return _fresh(_scan.scan(x, exclusive=exclusive, op=op, dim=dim), x)
+
+
+@scan_dim.register_fake
+def _(x, dim, op, exclusive=False):
     return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 
@@ -211,7 +223,7 @@ def _(x, flags):
 
 OPS = {
     "heat_step": heat_step, "heat_stepn": heat_stepn, "scan": scan, "scan_op": scan_op,
-    "segmented_scan": segmented_scan,
+    "scan_dim": scan_dim, "segmented_scan": segmented_scan,
     "sort": sort, "sort_by_key": sort_by_key, "argsort": argsort, "spmv_csr": spmv_csr, "transpose": transpose, "sgemm": sgemm,
     "gemv": gemv, "copy_if": copy_if,
 }

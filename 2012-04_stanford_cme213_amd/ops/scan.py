@@ -6,6 +6,10 @@
 * :func:`cummax` / :func:`cummin` (``scan(..., op="max" / "min")``) -- the
   running maximum / minimum, ``torch.cummax`` / ``torch.cummin`` values bit for
   bit, with ``algo="lookback"`` or ``"rts"``.
+* ``scan`` / ``cummax`` / ``cummin`` with ``dim=d`` -- the same along one
+  dimension of a tensor of any rank (``csrc/hip/scan_dim.hip``; no look-back,
+  chunked reduce-then-scan where the lines are few), :func:`summed_area_table`
+  on top of it, :func:`scan_dim_launch_info`.
 * :func:`reduce` -- sum / max / min; the lecture's shared-memory tree
   (``slides/Lecture05.pdf`` 15-16) as ``algo="tree"``.
 * Both take float32 / int32 and int64 / float64 (``scan`` also uint32); the
@@ -278,10 +282,12 @@ def _check_lookback(x: torch.Tensor, before: bool = False) -> None:
 
 
 def scan(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = None,
-         algo: str = "auto", op: str = "sum") -> torch.Tensor:
+         algo: str = "auto", op: str = "sum", dim: int | None = None) -> torch.Tensor:
     """Prefix sum of a 1-D contiguous float32/int32/uint32/int64/float64 tensor.
     ``op="max"`` / ``"min"``: the running maximum / minimum instead, see
-    :func:`cummax`.
+    :func:`cummax`. ``dim=None`` scans the flattened tensor; ``dim=d`` scans a
+    tensor of any rank along dimension ``d`` and returns a tensor of ``x``'s
+    shape, see :func:`_scan_dim`.
     algo: "auto" ("lookback" for 32-bit integers, whose sums are exact in any
     order; "rts" for float32 and float64, whose fixed summation tree is bitwise
     reproducible -- look-back's float prefixes depend on which predecessor had
@@ -301,6 +307,8 @@ def scan(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = No
     contiguous) may be ``x`` itself for "rts" and "lookback"."""
     if op not in _OPS:
         raise ValueError(f"scan: op {op!r} is not one of {sorted(_OPS)}")
+    if dim is not None:
+        return _scan_dim(x, exclusive, out, algo, op, dim)
     if op != "sum":
         return _scan_minmax(x, exclusive, out, algo, op)
     if not x.is_contiguous():
@@ -411,7 +419,7 @@ def _scan_minmax(x: torch.Tensor, exclusive: bool, out: torch.Tensor | None, alg
 
 
 def cummax(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = None,
-           algo: str = "auto") -> torch.Tensor:
+           algo: str = "auto", dim: int | None = None) -> torch.Tensor:
     """Running maximum of a 1-D float32/int32/uint32/int64/float64 tensor:
     ``out[i] = max(x[0..i])``, the values of ``torch.cummax(x, 0)`` bit for bit
     (no index output). NaN is sticky -- every output from the first NaN on is
@@ -423,15 +431,156 @@ def cummax(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = 
     ``algo``: "lookback" (single pass; also "auto" for every dtype: the
     operator is exactly associative, so the result does not depend on the order
     in which workgroups publish) or "rts" (reduce-then-scan); any other raises
-    a ``TypeError``. ``out``, alignment and the CPU backend as :func:`scan`."""
-    return scan(x, exclusive, out, algo, op="max")
+    a ``TypeError``. ``out``, alignment and the CPU backend as :func:`scan`.
+    ``dim=d``: ``torch.cummax(x, d).values`` of a tensor of any rank."""
+    return scan(x, exclusive, out, algo, op="max", dim=dim)
 
 
 def cummin(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = None,
-           algo: str = "auto") -> torch.Tensor:
+           algo: str = "auto", dim: int | None = None) -> torch.Tensor:
     """Running minimum: the mirror image of :func:`cummax` (identity ``+inf`` /
     the type's maximum)."""
-    return scan(x, exclusive, out, algo, op="min")
+    return scan(x, exclusive, out, algo, op="min", dim=dim)
+
+
+_ext.proto(_ext.HIP_PROTOS, "cme_scan_dim", "ppqqqiiipp")
+_ext.proto(_ext.HIP_PROTOS, "cme_scan_dim_info", "qqqiiip")
+_ext.proto(_ext.HIP_PROTOS, "cme_scan_dim_ws_bytes", "qqqip")
+_ext.proto(_ext.CPU_PROTOS, "cme_cpu_scan_dim", "ppqqqiii")
+
+_DIM_FORMS = ("flat", "row", "col")
+_retired_graph_ws: list = []
+
+
+def _dtype_code(dtype: torch.dtype) -> int:
+    if dtype in _DT64:
+        return _DT64[dtype]
+    if dtype in _DT_SCAN:
+        return _DT_SCAN[dtype]
+    raise TypeError(f"scan: {dtype} is not supported")
+
+
+def _split_dim(shape, dim: int) -> tuple[int, int, int]:
+    """(outer, n, inner) of scanning ``shape`` along ``dim``."""
+    nd = len(shape)
+    if nd == 0:
+        raise ValueError("scan: dim= needs a tensor of at least one dimension")
+    if not -nd <= dim < nd:
+        raise IndexError(f"scan: dim {dim} is out of range for a tensor of {nd} dimension(s)")
+    d = dim % nd
+    outer = inner = 1
+    for s in shape[:d]:
+        outer *= int(s)
+    for s in shape[d + 1:]:
+        inner *= int(s)
+    return outer, int(shape[d]), inner
+
+
+def _dim_ws(device: torch.device, nbytes: int) -> torch.Tensor | None:
+    """Chunk totals of a scan along a dimension, grown before the launch and
+    never under stream capture. Eager launches use a buffer per (device,
+    stream). A capture (whose stream is not the one of the warm-up) uses one
+    buffer per device, which every eager launch keeps at least as large as its
+    own, so the scan is run once before it is captured; a buffer that a graph
+    may still write to is kept alive when a larger one replaces it."""
+    if nbytes == 0:
+        return None
+    gkey = ("scan_dim:graph", device.index)
+    g = _ws_cache.get(gkey)
+    if torch.cuda.is_current_stream_capturing():
+        if g is None or g.numel() < nbytes:
+            raise RuntimeError("scan: the chunk-total workspace cannot grow under stream capture; "
+                               "run the scan once before capturing it")
+        return g
+    if g is None or g.numel() < nbytes:
+        if g is not None:
+            _retired_graph_ws.append(g)
+        _ws_cache[gkey] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
+    return workspace(device, nbytes, f"scan_dim:{_ext.stream_ptr(device)}")
+
+
+def _scan_dim(x: torch.Tensor, exclusive: bool, out: torch.Tensor | None, algo: str, op: str, dim: int) -> torch.Tensor:
+    """``scan(..., dim=d)``: the scan of a tensor of any rank along dimension
+    ``d``, seen as ``(outer, n, inner)`` with element ``(o, i, j)`` at
+    ``(o*n + i)*inner + j`` (``csrc/hip/scan_dim.hip``: the row form for
+    ``inner == 1``, the column form otherwise; CPU: ``cme_cpu_scan_dim``). The
+    rules are those of the 1-D scans: integer sums wrap, max / min are the
+    values of ``torch.cummax`` / ``torch.cummin``, ``exclusive`` starts every
+    line with the identity. Float sums are bitwise reproducible from run to
+    run: no kernel waits for another workgroup, ``n`` is split by chunked
+    reduce-then-scan where the lines alone cannot fill the device. ``out``
+    (contiguous, ``x``'s dtype, shape and device) may be ``x``. With
+    ``outer == inner == 1`` the call is the 1-D scan and takes its ``algo``;
+    otherwise ``algo`` must be "auto"."""
+    outer, n, inner = _split_dim(x.shape, dim)
+    code = _dtype_code(x.dtype)
+    if not x.is_contiguous():
+        x = x.contiguous()
+    if out is not None and (out.dtype != x.dtype or out.shape != x.shape or out.device != x.device
+                            or not out.is_contiguous()):
+        raise ValueError("scan: out must be a contiguous tensor of x's dtype, shape and device")
+    if outer == 1 and inner == 1 and n > 0:
+        flat = scan(x.reshape(-1), exclusive, None if out is None else out.reshape(-1), algo, op)
+        return flat.view(x.shape) if out is None else out
+    if algo != "auto":
+        raise TypeError(f"scan: algo {algo!r} is for the 1-D scans; a scan along a dimension of a batched shape "
+                        "takes algo='auto' only")
+    out = torch.empty_like(x) if out is None else out
+    if x.numel() == 0:
+        return out
+    if not x.is_cuda:
+        _ext.call_cpu("cme_cpu_scan_dim", x.data_ptr(), out.data_ptr(), outer, n, inner, code, _OPS[op], int(exclusive))
+        return out
+    import ctypes
+
+    nbytes = ctypes.c_longlong(0)
+    with torch.cuda.device(x.device):
+        _ext.call_hip("cme_scan_dim_ws_bytes", outer, n, inner, code, ctypes.addressof(nbytes))
+        ws = _dim_ws(x.device, nbytes.value)
+        _ext.call_hip("cme_scan_dim", x.data_ptr(), out.data_ptr(), outer, n, inner, code, _OPS[op], int(exclusive),
+                      None if ws is None else ws.data_ptr(), _ext.stream_ptr(x.device))
+    return out
+
+
+def scan_dim_launch_info(shape, dim: int, dtype: torch.dtype = torch.float32, op: str = "sum",
+                         exclusive: bool = False, device: torch.device | str = "cuda") -> dict:
+    """How ``scan(x, dim=dim)`` of a 16-byte aligned tensor of ``shape`` runs on
+    ``device``: ``form`` ("flat": the 1-D path, "row", "col"), ``outer``, ``n``,
+    ``inner``, ``chunks`` (K along ``n``; 1 is a single pass) of ``chunk``
+    elements, ``tile`` (elements of a line per workgroup -- or wave -- step;
+    column form: rows of loads in flight per lane), ``vector`` (elements per
+    lane access; 1 means scalar), ``waves`` (row form: waves that share a
+    line), ``workgroups`` and ``ws_bytes``. The CPU backend reports the shape
+    split only (``chunks`` 1, no workgroups)."""
+    import ctypes
+
+    if op not in _OPS:
+        raise ValueError(f"scan: op {op!r} is not one of {sorted(_OPS)}")
+    outer, n, inner = _split_dim(tuple(shape), dim)
+    code = _dtype_code(dtype)
+    form = 0 if outer == 1 and inner == 1 else 1 if inner == 1 else 2
+    d = {"form": _DIM_FORMS[form], "outer": outer, "n": n, "inner": inner, "chunks": 1, "chunk": n, "tile": 0,
+         "vector": 1, "waves": 0, "workgroups": 0, "ws_bytes": 0}
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        return d
+    info = (ctypes.c_longlong * 8)()
+    with torch.cuda.device(dev):
+        _ext.call_hip("cme_scan_dim_info", outer, n, inner, code, _OPS[op], int(exclusive), ctypes.addressof(info))
+    d.update(form=_DIM_FORMS[int(info[0])], chunks=int(info[1]), chunk=int(info[2]), tile=int(info[3]),
+             vector=int(info[4]), workgroups=int(info[5]), ws_bytes=int(info[6]), waves=int(info[7]))
+    return d
+
+
+def summed_area_table(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Summed-area table over the last two dimensions of ``x`` (any scan
+    dtype, at least 2-D): ``out[..., i, j] = sum(x[..., :i+1, :j+1])``, a row
+    scan (``dim=-1``) followed by a column scan (``dim=-2``) in place. The sum
+    of any box is then four look-ups. Integer sums wrap."""
+    if x.ndim < 2:
+        raise ValueError("summed_area_table: x must have at least two dimensions")
+    out = scan(x, out=out, dim=-1)
+    return scan(out, out=out, dim=-2)
 
 
 def reduce(x: torch.Tensor, op: str = "sum", algo: str = "vector") -> torch.Tensor:

@@ -10,6 +10,9 @@ per measurement with the reference number it is compared against.
   scan_minmax  running max (cummax) by look-back and reduce-then-scan against the
              sum look-back, torch.cummax and the copy of the same run, float32 /
              int32 / int64 / float64 at 2^25 and 2^27 (profiles/scan_minmax.md)
+  scan_dim   scans along one dimension, one shape per regime, float32 / int64,
+             against torch.cumsum(x, dim) and the copy of the same run
+             (profiles/scan_dim.md)
   spmvscan   the 15 final-project shapes (BASELINE #19-21, synthetic values)
   cipher     19.76 MB moby-dick x16 (BASELINE #1-3)
   pagerank   2^21 nodes, avg 8 edges, 20 iterations (BASELINE #5)
@@ -199,6 +202,50 @@ def main():
                          GBps=round(2 * size * n / ms / 1e6, 1),
                          share_of_copy=round(2 * size * n / ms / 1e6 / copy_bps, 3), **extra)
                 sc.check_lookback(dev)
+                del xs, ys, arms
+
+    if want("scan_dim"):
+        # Scans along one dimension, one shape per regime of csrc/hip/
+        # scan_dim.hip, against torch.cumsum(x, dim) and the copy of the same
+        # operands; measured like scan64 (three operand sets, arms alternated,
+        # every share against the copy of the same run). One max arm against
+        # torch.cummax. `ok`: our time does not exceed torch.cumsum's by more
+        # than the larger spread (max - min) the two arms show in this run.
+        shapes = [((65536, 2048), -1, "row, K == 1"), ((1 << 20, 64), -1, "row, short rows"),
+                  ((16, 1 << 22), -1, "row, K > 1"), ((8192, 8192), 0, "column, wide"),
+                  ((1 << 21, 64), 0, "column, tall and thin, K > 1"), ((64, 1 << 21), 0, "column, short and wide"),
+                  ((256, 512, 512), 1, "column"), ((1 << 22, 3), 0, "column, narrow")]
+        for dt in (torch.float32, torch.int64):
+            for shape, dim, regime in shapes:
+                if dt == torch.int64:
+                    xs = [torch.randint(-2 ** 40, 2 ** 40, shape, device=dev, dtype=dt) for _ in range(3)]
+                else:
+                    xs = [torch.rand(shape, device=dev, dtype=dt) for _ in range(3)]
+                ys = [torch.empty_like(x) for x in xs]
+                arms = {
+                    "copy": lambda k: ys[k].copy_(xs[k]),
+                    "scan_dim": lambda k: sc.scan(xs[k], out=ys[k], dim=dim),
+                    "torch.cumsum": lambda k: torch.cumsum(xs[k], dim, out=ys[k]),
+                }
+                if dt == torch.float32 and regime == "row, K == 1":
+                    arms["scan_dim-max"] = lambda k: sc.scan(xs[k], out=ys[k], op="max", dim=dim)
+                    arms["torch.cummax"] = lambda k: torch.cummax(xs[k], dim)
+                res = alternate(arms, rounds=8)
+                size, n = xs[0].element_size(), xs[0].numel()
+                info = sc.scan_dim_launch_info(shape, dim, dtype=dt, device=dev)
+                copy_bps = 2 * size * n / res["copy"][0] / 1e6
+                t_ms, t_lo, t_hi = res["torch.cumsum"]
+                for name, (ms, lo, hi) in res.items():
+                    extra = {}
+                    if name == "scan_dim":
+                        spread = max(hi - lo, t_hi - t_lo)
+                        extra = dict(form=info["form"], chunks=info["chunks"], vector=info["vector"],
+                                     workgroups=info["workgroups"], torch_ms=round(t_ms, 4),
+                                     spread_ms=round(spread, 4), ok=bool(ms <= t_ms + spread))
+                    emit(bench="scan_dim", dtype=str(dt).split(".")[1], shape=list(shape), dim=dim, regime=regime,
+                         arm=name, ms=round(ms, 4), ms_min=round(lo, 4), ms_max=round(hi, 4),
+                         model_B_per_elem=2 * size, GBps=round(2 * size * n / ms / 1e6, 1),
+                         share_of_copy=round(2 * size * n / ms / 1e6 / copy_bps, 3), **extra)
                 del xs, ys, arms
 
     if want("spmvscan"):

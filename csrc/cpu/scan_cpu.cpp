@@ -161,6 +161,99 @@ CME_CPU_EXPORT int cme_cpu_scan_op(const void* in, void* out, long long n, int d
     return 1;
 }
 
+namespace {
+
+struct Sum {
+    template <typename T> T operator()(T a, T b) const { return a + b; }
+    template <typename T> static T identity() { return T(0); }
+};
+
+// Scan of (outer, n, inner) along n: element (o, i, j) at (o*n + i)*inner + j.
+// A work item is a block of up to kColBlock adjacent columns of one `o` (a row
+// when inner == 1), walked down i with the running values in a small array.
+// Where there are fewer such lines than threads, n is split into K chunks and
+// the three phases of scan_op_impl run over (line, chunk) items: totals, their
+// serial exclusive scan along the chunks, the rescan from each chunk's carry.
+// op is always called as op(earlier, later); out may be in.
+constexpr long long kColBlock = 512;
+
+template <typename T, typename Op>
+void scan_dim_impl(const T* in, T* out, long long outer, long long n, long long inner, bool exclusive, Op op) {
+    const T id = Op::template identity<T>();
+    const long long nb = (inner + kColBlock - 1) / kColBlock;
+    const long long lines = outer * nb;
+    const int nt = omp_get_max_threads();
+    long long K = 1;
+    if (lines < nt) K = (nt + lines - 1) / lines;
+    if (K > n) K = n;
+    const long long chunk = (n + K - 1) / K;
+    std::vector<T> tot;
+    if (K > 1) tot.assign((std::size_t)(outer * K * inner), id);
+    auto walk = [&](long long item, bool totals_only) {
+        const long long b = item % nb, k = (item / nb) % K, o = item / (nb * K);
+        const long long j0 = b * kColBlock, w = (j0 + kColBlock < inner ? j0 + kColBlock : inner) - j0;
+        const long long i0 = k * chunk < n ? k * chunk : n, i1 = i0 + chunk < n ? i0 + chunk : n;
+        T* t = K > 1 ? tot.data() + (o * K + k) * inner + j0 : nullptr;
+        T run[kColBlock];
+        for (long long j = 0; j < w; ++j) run[j] = (K > 1 && !totals_only) ? t[j] : id;
+        for (long long i = i0; i < i1; ++i) {
+            const T* p = in + (o * n + i) * inner + j0;
+            T* q = out + (o * n + i) * inner + j0;
+            for (long long j = 0; j < w; ++j) {
+                const T inc = op(run[j], p[j]);
+                if (!totals_only) q[j] = exclusive ? run[j] : inc;
+                run[j] = inc;
+            }
+        }
+        if (totals_only)
+            for (long long j = 0; j < w; ++j) t[j] = run[j];
+    };
+    const long long items = lines * K;
+    if (K > 1) {
+#pragma omp parallel for schedule(static)
+        for (long long item = 0; item < items; ++item) walk(item, true);
+#pragma omp parallel for schedule(static)
+        for (long long c = 0; c < outer * inner; ++c) {
+            T* t = tot.data() + (c / inner) * K * inner + c % inner;
+            T run = id;
+            for (long long k = 0; k < K; ++k) {
+                const T v = t[k * inner];
+                t[k * inner] = run;
+                run = op(run, v);
+            }
+        }
+    }
+#pragma omp parallel for schedule(static)
+    for (long long item = 0; item < items; ++item) walk(item, false);
+}
+
+template <typename T, typename S>
+int scan_dim_dispatch(const void* in, void* out, long long outer, long long n, long long inner, int op, bool exclusive) {
+    // S: the unsigned type integer sums wrap in (T itself for the floats)
+    if (op == 0) scan_dim_impl((const S*)in, (S*)out, outer, n, inner, exclusive, Sum());
+    else if (op == 1) scan_dim_impl((const T*)in, (T*)out, outer, n, inner, exclusive, CumMax());
+    else if (op == 2) scan_dim_impl((const T*)in, (T*)out, outer, n, inner, exclusive, CumMin());
+    else return 1;
+    return 0;
+}
+
+}  // namespace
+
+// Scan along the middle dimension of a contiguous (outer, n, inner) tensor.
+// dtype as cme_cpu_scan, op as cme_cpu_scan_op, the same rules: integer sums
+// wrap, max / min are torch.cummax / cummin values.
+CME_CPU_EXPORT int cme_cpu_scan_dim(const void* in, void* out, long long outer, long long n, long long inner,
+                                    int dtype, int op, int exclusive) {
+    if (outer < 0 || n < 0 || inner < 0) return 1;
+    if (outer == 0 || n == 0 || inner == 0) return 0;
+    if (dtype == 0) return scan_dim_dispatch<float, float>(in, out, outer, n, inner, op, exclusive);
+    if (dtype == 1) return scan_dim_dispatch<int32_t, uint32_t>(in, out, outer, n, inner, op, exclusive);
+    if (dtype == 2) return scan_dim_dispatch<uint32_t, uint32_t>(in, out, outer, n, inner, op, exclusive);
+    if (dtype == 3) return scan_dim_dispatch<int64_t, uint64_t>(in, out, outer, n, inner, op, exclusive);
+    if (dtype == 4) return scan_dim_dispatch<double, double>(in, out, outer, n, inner, op, exclusive);
+    return 1;
+}
+
 CME_CPU_EXPORT int cme_cpu_reduce(const void* in, long long n, int dtype, int op, void* out) {
     if (n <= 0) return 1;
     if (dtype == 0) reduce_impl((const float*)in, n, op, (float*)out);

@@ -46,6 +46,8 @@ enum TuneKey : int {
     kTuneMergeBlock,       // CME_MERGE_BLOCK: merge sort block-sort tile, 8192 (512 lanes) or 16384 keys (1024 lanes); 0 auto (16384 for keys only from 4M)
     kTuneMergeSamples,     // CME_MERGE_SAMPLES: merge sort run samples narrowing each partition search (1 on, 0 off)
     kTuneMergeBlockSort,   // CME_MERGE_BLOCK_SORT: keys-only 16384-key block sort, 1 LDS radix (4 digit passes), 0 merge network
+    kTuneScanDimChunks,    // CME_SCAN_DIM_CHUNKS: chunks along the scanned dimension of scan(dim=) (0 = rule)
+    kTuneScanDimMaxBlocks, // CME_SCAN_DIM_MAXBLOCKS: grid cap of the scan(dim=) kernels (0 = rule)
     kTuneCount
 };
 
