@@ -16,6 +16,7 @@ Ops (schema in each docstring; "!" = mutated in place):
 ``scan``                  inclusive / exclusive prefix sum
 ``scan_op``               inclusive / exclusive prefix sum / running max / running min
 ``scan_dim``              the same along one dimension of a tensor of any rank
+``cummax`` / ``cummin``   running max / min along a dimension: (values, int64 indices)
 ``segmented_scan``        inclusive segmented sum scan (uint8 heads or int32 bitmask)
 ``sort`` / ``sort_by_key`` stable LSD radix sort, 32- and 64-bit keys (+ 4- / 8-byte values)
 ``argsort``               int64 stable sorting permutation (ascending or descending)
@@ -112,6 +113,32 @@ def scan_dim(x: Tensor, dim: int, op: str, exclusive: bool = False) -> Tensor:
 @scan_dim.register_fake
 def _(x, dim, op, exclusive=False):
     return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
+@torch.library.custom_op(f"{NS}::cummax", mutates_args=())
+def cummax(x: Tensor, dim: int) -> tuple[Tensor, Tensor]:
+    """cummax(Tensor x, int dim) -> (Tensor, Tensor)   (values, int64 indices along ``dim``: ``torch.cummax``)"""
+    v, i = _scan.cummax(x, dim=dim, return_indices=True)
+    return _fresh(v, x), i
+
+
+@cummax.register_fake
+def _(x, dim):
+    return (torch.empty_like(x, memory_format=torch.contiguous_format),
+            torch.empty(x.shape, dtype=torch.int64, device=x.device))
+
+
+@torch.library.custom_op(f"{NS}::cummin", mutates_args=())
+def cummin(x: Tensor, dim: int) -> tuple[Tensor, Tensor]:
+    """cummin(Tensor x, int dim) -> (Tensor, Tensor)   (values, int64 indices along ``dim``: ``torch.cummin``)"""
+    v, i = _scan.cummin(x, dim=dim, return_indices=True)
+    return _fresh(v, x), i
+
+
+@cummin.register_fake
+def _(x, dim):
+    return (torch.empty_like(x, memory_format=torch.contiguous_format),
+            torch.empty(x.shape, dtype=torch.int64, device=x.device))
 
 
 @torch.library.custom_op(f"{NS}::segmented_scan", mutates_args=())
@@ -223,7 +250,7 @@ def _(x, flags):
 
 OPS = {
     "heat_step": heat_step, "heat_stepn": heat_stepn, "scan": scan, "scan_op": scan_op,
-    "scan_dim": scan_dim, "segmented_scan": segmented_scan,
+    "scan_dim": scan_dim, "cummax": cummax, "cummin": cummin, "segmented_scan": segmented_scan,
     "sort": sort, "sort_by_key": sort_by_key, "argsort": argsort, "spmv_csr": spmv_csr, "transpose": transpose, "sgemm": sgemm,
     "gemv": gemv, "copy_if": copy_if,
 }

@@ -10,6 +10,10 @@
   dimension of a tensor of any rank (``csrc/hip/scan_dim.hip``; no look-back,
   chunked reduce-then-scan where the lines are few), :func:`summed_area_table`
   on top of it, :func:`scan_dim_launch_info`.
+* ``cummax`` / ``cummin`` with ``return_indices=True`` -- ``(values, indices)``
+  as ``torch.cummax`` / ``torch.cummin`` return them, along any dimension or
+  over the flattened tensor (``csrc/hip/scan_dim_arg.hip``: the same batched
+  kernels with a (value, index) carry).
 * :func:`reduce` -- sum / max / min; the lecture's shared-memory tree
   (``slides/Lecture05.pdf`` 15-16) as ``algo="tree"``.
 * Both take float32 / int32 and int64 / float64 (``scan`` also uint32); the
@@ -24,6 +28,8 @@
 CPU tensors use the OpenMP oracles in ``csrc/cpu/scan_cpu.cpp``.
 """
 from __future__ import annotations
+
+import collections
 
 import torch
 
@@ -282,12 +288,13 @@ def _check_lookback(x: torch.Tensor, before: bool = False) -> None:
 
 
 def scan(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = None,
-         algo: str = "auto", op: str = "sum", dim: int | None = None) -> torch.Tensor:
+         algo: str = "auto", op: str = "sum", dim: int | None = None, return_indices: bool = False):
     """Prefix sum of a 1-D contiguous float32/int32/uint32/int64/float64 tensor.
     ``op="max"`` / ``"min"``: the running maximum / minimum instead, see
     :func:`cummax`. ``dim=None`` scans the flattened tensor; ``dim=d`` scans a
     tensor of any rank along dimension ``d`` and returns a tensor of ``x``'s
-    shape, see :func:`_scan_dim`.
+    shape, see :func:`_scan_dim`. ``return_indices=True`` (max / min only):
+    the named pair ``(values, indices)`` of :func:`_cumarg`.
     algo: "auto" ("lookback" for 32-bit integers, whose sums are exact in any
     order; "rts" for float32 and float64, whose fixed summation tree is bitwise
     reproducible -- look-back's float prefixes depend on which predecessor had
@@ -307,6 +314,8 @@ def scan(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = No
     contiguous) may be ``x`` itself for "rts" and "lookback"."""
     if op not in _OPS:
         raise ValueError(f"scan: op {op!r} is not one of {sorted(_OPS)}")
+    if return_indices:
+        return _cumarg(x, exclusive, out, algo, op, dim)
     if dim is not None:
         return _scan_dim(x, exclusive, out, algo, op, dim)
     if op != "sum":
@@ -419,10 +428,10 @@ def _scan_minmax(x: torch.Tensor, exclusive: bool, out: torch.Tensor | None, alg
 
 
 def cummax(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = None,
-           algo: str = "auto", dim: int | None = None) -> torch.Tensor:
+           algo: str = "auto", dim: int | None = None, return_indices: bool = False):
     """Running maximum of a 1-D float32/int32/uint32/int64/float64 tensor:
-    ``out[i] = max(x[0..i])``, the values of ``torch.cummax(x, 0)`` bit for bit
-    (no index output). NaN is sticky -- every output from the first NaN on is
+    ``out[i] = max(x[0..i])``, the values of ``torch.cummax(x, 0)`` bit for bit.
+    NaN is sticky -- every output from the first NaN on is
     NaN -- and among equal values the later element wins, which shows only
     between ``+0.0`` and ``-0.0``. ``exclusive``: ``out[0]`` is the identity
     (``-inf``; the type's minimum for integers) and ``out[i]`` the inclusive
@@ -432,15 +441,20 @@ def cummax(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = 
     operator is exactly associative, so the result does not depend on the order
     in which workgroups publish) or "rts" (reduce-then-scan); any other raises
     a ``TypeError``. ``out``, alignment and the CPU backend as :func:`scan`.
-    ``dim=d``: ``torch.cummax(x, d).values`` of a tensor of any rank."""
-    return scan(x, exclusive, out, algo, op="max", dim=dim)
+    ``dim=d``: ``torch.cummax(x, d).values`` of a tensor of any rank.
+
+    ``return_indices=True``: the named pair ``(values, indices)`` of
+    ``torch.cummax`` -- ``values`` as above, ``indices`` the int64 position of
+    the winner along ``dim`` (in the flattened tensor for ``dim=None``), the
+    later of equal values and of NaNs; see :func:`_cumarg`."""
+    return scan(x, exclusive, out, algo, op="max", dim=dim, return_indices=return_indices)
 
 
 def cummin(x: torch.Tensor, exclusive: bool = False, out: torch.Tensor | None = None,
-           algo: str = "auto", dim: int | None = None) -> torch.Tensor:
+           algo: str = "auto", dim: int | None = None, return_indices: bool = False):
     """Running minimum: the mirror image of :func:`cummax` (identity ``+inf`` /
     the type's maximum)."""
-    return scan(x, exclusive, out, algo, op="min", dim=dim)
+    return scan(x, exclusive, out, algo, op="min", dim=dim, return_indices=return_indices)
 
 
 _ext.proto(_ext.HIP_PROTOS, "cme_scan_dim", "ppqqqiiipp")
@@ -476,16 +490,19 @@ def _split_dim(shape, dim: int) -> tuple[int, int, int]:
     return outer, int(shape[d]), inner
 
 
-def _dim_ws(device: torch.device, nbytes: int) -> torch.Tensor | None:
+def _dim_ws(device: torch.device, nbytes: int, family: str = "scan_dim") -> torch.Tensor | None:
     """Chunk totals of a scan along a dimension, grown before the launch and
     never under stream capture. Eager launches use a buffer per (device,
     stream). A capture (whose stream is not the one of the warm-up) uses one
     buffer per device, which every eager launch keeps at least as large as its
     own, so the scan is run once before it is captured; a buffer that a graph
-    may still write to is kept alive when a larger one replaces it."""
+    may still write to is kept alive when a larger one replaces it. ``family``
+    keeps the buffers of the indexed scans ("cumarg_dim") apart from those of
+    the values-only ones: a captured scan of one kind never shares its totals
+    with a scan of the other."""
     if nbytes == 0:
         return None
-    gkey = ("scan_dim:graph", device.index)
+    gkey = (f"{family}:graph", device.index)
     g = _ws_cache.get(gkey)
     if torch.cuda.is_current_stream_capturing():
         if g is None or g.numel() < nbytes:
@@ -496,7 +513,7 @@ def _dim_ws(device: torch.device, nbytes: int) -> torch.Tensor | None:
         if g is not None:
             _retired_graph_ws.append(g)
         _ws_cache[gkey] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
-    return workspace(device, nbytes, f"scan_dim:{_ext.stream_ptr(device)}")
+    return workspace(device, nbytes, f"{family}:{_ext.stream_ptr(device)}")
 
 
 def _scan_dim(x: torch.Tensor, exclusive: bool, out: torch.Tensor | None, algo: str, op: str, dim: int) -> torch.Tensor:
@@ -542,8 +559,82 @@ def _scan_dim(x: torch.Tensor, exclusive: bool, out: torch.Tensor | None, algo: 
     return out
 
 
+_ext.proto(_ext.HIP_PROTOS, "cme_cumarg_dim", "pppqqqiipp")
+_ext.proto(_ext.HIP_PROTOS, "cme_cumarg_dim_info", "qqqiip")
+_ext.proto(_ext.HIP_PROTOS, "cme_cumarg_dim_ws_bytes", "qqqip")
+_ext.proto(_ext.CPU_PROTOS, "cme_cpu_cumarg_dim", "pppqqqii")
+
+ScanWithIndices = collections.namedtuple("ScanWithIndices", ["values", "indices"])
+
+
+def _cumarg(x: torch.Tensor, exclusive: bool, out, algo: str, op: str, dim: int | None) -> ScanWithIndices:
+    """``cummax`` / ``cummin`` with ``return_indices=True``: the named pair
+    ``(values, indices)`` of ``torch.cummax`` / ``torch.cummin``. ``values`` is
+    what the call without indices returns, bit for bit; ``indices`` is int64,
+    contiguous, of ``x``'s shape: the position along ``dim`` (in the flattened
+    tensor for ``dim=None``) of the element the running value comes from. Of
+    equal values (``+0.0`` / ``-0.0`` included) the later one is named, a
+    later NaN takes the index from an earlier one, and every output has a real
+    index, a line of all ``-inf`` or all type-minimum too.
+
+    The tensor is seen as ``(outer, n, inner)`` like :func:`_scan_dim` and run
+    by the kernels of ``csrc/hip/scan_dim_arg.hip`` under the same launch plan
+    (:func:`scan_dim_launch_info` with ``indices=True``); a single line, the
+    flattened case included, is a row chunked across the device -- the
+    look-back kernels have no index output. CPU: ``cme_cpu_cumarg_dim``.
+    ``out`` may be a pair ``(values_out, indices_out)`` of contiguous tensors
+    of ``x``'s shape and device (``x``'s dtype and int64); ``values_out`` may
+    be ``x``, ``indices_out`` must overlap neither. There is no exclusive mode
+    (element 0 would have no index) and ``algo`` must be "auto". The chunk
+    totals have buffers of their own, apart from those of the values-only
+    scans; under stream capture the same rule holds: run the call once before
+    capturing it."""
+    if op == "sum":
+        raise ValueError("scan: return_indices is for op='max' / 'min'; a sum has no index")
+    if exclusive:
+        raise ValueError("scan: return_indices has no exclusive mode (element 0 would have no index)")
+    if algo != "auto":
+        raise TypeError(f"scan: algo {algo!r} has no index output; return_indices takes algo='auto' only")
+    if x.ndim == 0:
+        raise ValueError("scan: return_indices needs a tensor of at least one dimension")
+    outer, n, inner = (1, x.numel(), 1) if dim is None else _split_dim(x.shape, dim)
+    code = _dtype_code(x.dtype)
+    if out is None:
+        vout = iout = None
+    elif isinstance(out, (tuple, list)) and len(out) == 2 and all(isinstance(t, torch.Tensor) for t in out):
+        vout, iout = out
+    else:
+        raise ValueError("scan: with return_indices, out must be a pair (values_out, indices_out) of tensors")
+    if not x.is_contiguous():
+        x = x.contiguous()
+    if vout is not None and (vout.dtype != x.dtype or vout.shape != x.shape or vout.device != x.device
+                             or not vout.is_contiguous()):
+        raise ValueError("scan: values out must be a contiguous tensor of x's dtype, shape and device")
+    if iout is not None and (iout.dtype != torch.int64 or iout.shape != x.shape or iout.device != x.device
+                             or not iout.is_contiguous()):
+        raise ValueError("scan: indices out must be a contiguous int64 tensor of x's shape and device")
+    vout = torch.empty_like(x) if vout is None else vout
+    iout = torch.empty(x.shape, dtype=torch.int64, device=x.device) if iout is None else iout
+    res = ScanWithIndices(vout, iout)
+    if x.numel() == 0:
+        return res
+    if not x.is_cuda:
+        _ext.call_cpu("cme_cpu_cumarg_dim", x.data_ptr(), vout.data_ptr(), iout.data_ptr(), outer, n, inner, code,
+                      _OPS[op])
+        return res
+    import ctypes
+
+    nbytes = ctypes.c_longlong(0)
+    with torch.cuda.device(x.device):
+        _ext.call_hip("cme_cumarg_dim_ws_bytes", outer, n, inner, code, ctypes.addressof(nbytes))
+        ws = _dim_ws(x.device, nbytes.value, "cumarg_dim")
+        _ext.call_hip("cme_cumarg_dim", x.data_ptr(), vout.data_ptr(), iout.data_ptr(), outer, n, inner, code,
+                      _OPS[op], None if ws is None else ws.data_ptr(), _ext.stream_ptr(x.device))
+    return res
+
+
 def scan_dim_launch_info(shape, dim: int, dtype: torch.dtype = torch.float32, op: str = "sum",
-                         exclusive: bool = False, device: torch.device | str = "cuda") -> dict:
+                         exclusive: bool = False, device: torch.device | str = "cuda", indices: bool = False) -> dict:
     """How ``scan(x, dim=dim)`` of a 16-byte aligned tensor of ``shape`` runs on
     ``device``: ``form`` ("flat": the 1-D path, "row", "col"), ``outer``, ``n``,
     ``inner``, ``chunks`` (K along ``n``; 1 is a single pass) of ``chunk``
@@ -551,11 +642,22 @@ def scan_dim_launch_info(shape, dim: int, dtype: torch.dtype = torch.float32, op
     column form: rows of loads in flight per lane), ``vector`` (elements per
     lane access; 1 means scalar), ``waves`` (row form: waves that share a
     line), ``workgroups`` and ``ws_bytes``. The CPU backend reports the shape
-    split only (``chunks`` 1, no workgroups)."""
+    split only (``chunks`` 1, no workgroups).
+
+    ``indices=True`` (inclusive only; the plan does not depend on ``op``, and
+    the default "sum" is read as "max"): the plan of the indexed kernels behind
+    ``return_indices=True``. It is the same plan; ``tile`` is that of the
+    indexed row kernels, ``ws_bytes`` holds the value and the int64 index
+    totals, and "flat" (a single line) runs as a row chunked across the device,
+    not as the 1-D look-back scan."""
     import ctypes
 
     if op not in _OPS:
         raise ValueError(f"scan: op {op!r} is not one of {sorted(_OPS)}")
+    if indices:
+        op = "max" if op == "sum" else op
+        if exclusive:
+            raise ValueError("scan: return_indices has no exclusive mode")
     outer, n, inner = _split_dim(tuple(shape), dim)
     code = _dtype_code(dtype)
     form = 0 if outer == 1 and inner == 1 else 1 if inner == 1 else 2
@@ -566,7 +668,10 @@ def scan_dim_launch_info(shape, dim: int, dtype: torch.dtype = torch.float32, op
         return d
     info = (ctypes.c_longlong * 8)()
     with torch.cuda.device(dev):
-        _ext.call_hip("cme_scan_dim_info", outer, n, inner, code, _OPS[op], int(exclusive), ctypes.addressof(info))
+        if indices:
+            _ext.call_hip("cme_cumarg_dim_info", outer, n, inner, code, _OPS[op], ctypes.addressof(info))
+        else:
+            _ext.call_hip("cme_scan_dim_info", outer, n, inner, code, _OPS[op], int(exclusive), ctypes.addressof(info))
     d.update(form=_DIM_FORMS[int(info[0])], chunks=int(info[1]), chunk=int(info[2]), tile=int(info[3]),
              vector=int(info[4]), workgroups=int(info[5]), ws_bytes=int(info[6]), waves=int(info[7]))
     return d

@@ -13,6 +13,9 @@ per measurement with the reference number it is compared against.
   scan_dim   scans along one dimension, one shape per regime, float32 / int64,
              against torch.cumsum(x, dim) and the copy of the same run
              (profiles/scan_dim.md)
+  scan_arg   cummax with indices along a dimension and flattened, float32 / int64,
+             against the values-only scan, torch.cummax and the copy of the same
+             run (profiles/scan_cumarg.md)
   spmvscan   the 15 final-project shapes (BASELINE #19-21, synthetic values)
   cipher     19.76 MB moby-dick x16 (BASELINE #1-3)
   pagerank   2^21 nodes, avg 8 edges, 20 iterations (BASELINE #5)
@@ -247,6 +250,61 @@ def main():
                          model_B_per_elem=2 * size, GBps=round(2 * size * n / ms / 1e6, 1),
                          share_of_copy=round(2 * size * n / ms / 1e6 / copy_bps, 3), **extra)
                 del xs, ys, arms
+
+    if want("scan_arg"):
+        # cummax with indices (csrc/hip/scan_dim_arg.hip) against the values-only
+        # scan along the same dimension, torch.cummax (values and indices, as
+        # ours) and the copy of the same values; measured like scan_dim (three
+        # operand sets, arms alternated and reshuffled, an event pair per call).
+        # The byte bound: the indexed scan moves 2 * esize + 8 bytes per element
+        # in a single pass and 3 * esize + 8 when chunked, the copy 2 * esize;
+        # `pct_of_bound` is that bound at the copy rate of the same run over our
+        # time. `ok`: our median does not exceed torch.cummax's by more than the
+        # larger spread (max - min) the two arms show in this run. Plateau data
+        # (values in 0..15): the index moves while the value stands still.
+        shapes = [((1 << 25,), None, "1-D"), ((1 << 27,), None, "1-D"), ((65536, 2048), -1, "row, K == 1"),
+                  ((1 << 20, 64), -1, "row, short rows"), ((16, 1 << 22), -1, "row, K > 1"),
+                  ((8192, 8192), 0, "column, wide"), ((256, 512, 512), 1, "column"),
+                  ((64, 1 << 21), 0, "column, short and wide")]
+        for dt in (torch.float32, torch.int64):
+            for shape, dim, regime in shapes:
+                xs = [torch.randint(0, 16, shape, device=dev).to(dt) for _ in range(3)]
+                ys = [torch.empty_like(x) for x in xs]
+                idx = [torch.empty(shape, dtype=torch.int64, device=dev) for _ in range(3)]
+                tdim = 0 if dim is None else dim
+                arms = {
+                    "copy": lambda k: ys[k].copy_(xs[k]),
+                    "scan_dim-max": lambda k: sc.scan(xs[k], out=ys[k], op="max", dim=tdim),
+                    "cummax+indices": lambda k: sc.cummax(xs[k], dim=dim, return_indices=True, out=(ys[k], idx[k])),
+                }
+                torch_arm = lambda k: torch.cummax(xs[k], tdim, out=(ys[k], idx[k]))  # noqa: E731
+                if dim is None:
+                    # torch.cummax takes about 0.4 s per call on the 1-D shapes: fewer rounds, with
+                    # our arm alternating beside it (its reading of the main run is the one reported)
+                    res = alternate(arms, rounds=8)
+                    few = alternate({"torch.cummax": torch_arm, "ours": arms["cummax+indices"]}, rounds=3, warm=1)
+                    res["torch.cummax"] = few["torch.cummax"]
+                else:
+                    arms["torch.cummax"] = torch_arm
+                    res = alternate(arms, rounds=8)
+                size, n = xs[0].element_size(), xs[0].numel()
+                info = sc.scan_dim_launch_info(shape, tdim, dtype=dt, op="max", device=dev, indices=True)
+                copy_bps = 2 * size * n / res["copy"][0] / 1e6
+                per = (2 if info["chunks"] == 1 else 3) * size + 8
+                t_ms, t_lo, t_hi = res["torch.cummax"]
+                for name, (ms, lo, hi) in res.items():
+                    extra = {}
+                    if name == "cummax+indices":
+                        spread = max(hi - lo, t_hi - t_lo)
+                        extra = dict(form=info["form"], chunks=info["chunks"], tile=info["tile"], vector=info["vector"],
+                                     waves=info["waves"], workgroups=info["workgroups"], ws_bytes=info["ws_bytes"],
+                                     bound_B_per_elem=per, pct_of_bound=round(100 * per * n / copy_bps / 1e6 / ms, 1),
+                                     torch_ms=round(t_ms, 4), spread_ms=round(spread, 4), ok=bool(ms <= t_ms + spread))
+                    emit(bench="scan_arg", dtype=str(dt).split(".")[1], shape=list(shape), dim=dim, regime=regime,
+                         arm=name, ms=round(ms, 4), ms_min=round(lo, 4), ms_max=round(hi, 4),
+                         GBps=round((2 * size + (0 if name in ("copy", "scan_dim-max") else 8)) * n / ms / 1e6, 1),
+                         **extra)
+                del xs, ys, idx, arms
 
     if want("spmvscan"):
         from cme213x.models.spmv_scan import BENCH_SHAPES, REF_MS, SpmvScanSolver, generate

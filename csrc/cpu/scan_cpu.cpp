@@ -254,6 +254,126 @@ CME_CPU_EXPORT int cme_cpu_scan_dim(const void* in, void* out, long long outer, 
     return 1;
 }
 
+namespace {
+
+// Running max / min with the position of the winner (torch.cummax / cummin:
+// values and indices). The carry is a pair (v, i), i the position along n or
+// -1 for "none"; pairs join with the earlier operand first, and the later one
+// replaces it iff it is not none and passes the test of CumMax / CumMin. So a
+// later NaN or equal value takes the index, and a real element always beats
+// the identity value.
+struct ArgMax {
+    using Val = CumMax;
+    template <typename T> static bool later(T a, T b) { return b >= a || b != b; }
+};
+struct ArgMin {
+    using Val = CumMin;
+    template <typename T> static bool later(T a, T b) { return b <= a || b != b; }
+};
+
+template <typename A, typename T>
+inline void join(T& av, long long& ai, T bv, long long bi) {
+    if (bi >= 0 && A::later(av, bv)) {
+        av = bv;
+        ai = bi;
+    }
+}
+
+// The three phases of scan_dim_impl over pairs: pair totals of every (line,
+// chunk) item, their serial exclusive scan along the chunks, the rescan of
+// each chunk from its carry pair. out may be in.
+template <typename T, typename A>
+void cumarg_dim_impl(const T* in, T* out, long long* idx, long long outer, long long n, long long inner) {
+    const T id = A::Val::template identity<T>();
+    const long long nb = (inner + kColBlock - 1) / kColBlock;
+    const long long lines = outer * nb;
+    const int nt = omp_get_max_threads();
+    long long K = 1;
+    if (lines < nt) K = (nt + lines - 1) / lines;
+    if (K > n) K = n;
+    const long long chunk = (n + K - 1) / K;
+    std::vector<T> totv;
+    std::vector<long long> toti;
+    if (K > 1) {
+        totv.assign((std::size_t)(outer * K * inner), id);
+        toti.assign((std::size_t)(outer * K * inner), -1);
+    }
+    auto walk = [&](long long item, bool totals_only) {
+        const long long b = item % nb, k = (item / nb) % K, o = item / (nb * K);
+        const long long j0 = b * kColBlock, w = (j0 + kColBlock < inner ? j0 + kColBlock : inner) - j0;
+        const long long i0 = k * chunk < n ? k * chunk : n, i1 = i0 + chunk < n ? i0 + chunk : n;
+        const long long at = (o * K + k) * inner + j0;
+        T run[kColBlock];
+        long long runi[kColBlock];
+        for (long long j = 0; j < w; ++j) {
+            const bool seeded = K > 1 && !totals_only;
+            run[j] = seeded ? totv[at + j] : id;
+            runi[j] = seeded ? toti[at + j] : -1;
+        }
+        for (long long i = i0; i < i1; ++i) {
+            const long long row = (o * n + i) * inner + j0;
+            for (long long j = 0; j < w; ++j) {
+                join<A>(run[j], runi[j], in[row + j], i);
+                if (!totals_only) {
+                    out[row + j] = run[j];
+                    idx[row + j] = runi[j];
+                }
+            }
+        }
+        if (totals_only)
+            for (long long j = 0; j < w; ++j) {
+                totv[at + j] = run[j];
+                toti[at + j] = runi[j];
+            }
+    };
+    const long long items = lines * K;
+    if (K > 1) {
+#pragma omp parallel for schedule(static)
+        for (long long item = 0; item < items; ++item) walk(item, true);
+#pragma omp parallel for schedule(static)
+        for (long long c = 0; c < outer * inner; ++c) {
+            const long long at = (c / inner) * K * inner + c % inner;
+            T run = id;
+            long long runi = -1;
+            for (long long k = 0; k < K; ++k) {
+                const T v = totv[at + k * inner];
+                const long long vi = toti[at + k * inner];
+                totv[at + k * inner] = run;
+                toti[at + k * inner] = runi;
+                join<A>(run, runi, v, vi);
+            }
+        }
+    }
+#pragma omp parallel for schedule(static)
+    for (long long item = 0; item < items; ++item) walk(item, false);
+}
+
+template <typename T>
+int cumarg_dim_dispatch(const void* in, void* out, void* idx, long long outer, long long n, long long inner, int op) {
+    if (op == 1) cumarg_dim_impl<T, ArgMax>((const T*)in, (T*)out, (long long*)idx, outer, n, inner);
+    else if (op == 2) cumarg_dim_impl<T, ArgMin>((const T*)in, (T*)out, (long long*)idx, outer, n, inner);
+    else return 1;
+    return 0;
+}
+
+}  // namespace
+
+// Running max (op 1) / min (op 2) along the middle dimension of a contiguous
+// (outer, n, inner) tensor with the position of the winner along n: the
+// (values, indices) of torch.cummax / cummin. dtype as cme_cpu_scan;
+// out_values may be in, out_indices is int64.
+CME_CPU_EXPORT int cme_cpu_cumarg_dim(const void* in, void* out_values, void* out_indices, long long outer,
+                                      long long n, long long inner, int dtype, int op) {
+    if (outer < 0 || n < 0 || inner < 0) return 1;
+    if (outer == 0 || n == 0 || inner == 0) return 0;
+    if (dtype == 0) return cumarg_dim_dispatch<float>(in, out_values, out_indices, outer, n, inner, op);
+    if (dtype == 1) return cumarg_dim_dispatch<int32_t>(in, out_values, out_indices, outer, n, inner, op);
+    if (dtype == 2) return cumarg_dim_dispatch<uint32_t>(in, out_values, out_indices, outer, n, inner, op);
+    if (dtype == 3) return cumarg_dim_dispatch<int64_t>(in, out_values, out_indices, outer, n, inner, op);
+    if (dtype == 4) return cumarg_dim_dispatch<double>(in, out_values, out_indices, outer, n, inner, op);
+    return 1;
+}
+
 CME_CPU_EXPORT int cme_cpu_reduce(const void* in, long long n, int dtype, int op, void* out) {
     if (n <= 0) return 1;
     if (dtype == 0) reduce_impl((const float*)in, n, op, (float*)out);
