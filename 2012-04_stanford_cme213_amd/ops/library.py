@@ -17,6 +17,8 @@ Ops (schema in each docstring; "!" = mutated in place):
 ``scan_op``               inclusive / exclusive prefix sum / running max / running min
 ``scan_dim``              the same along one dimension of a tensor of any rank
 ``cummax`` / ``cummin``   running max / min along a dimension: (values, int64 indices)
+``reduce_dim``            sum / max / min along a dimension (``keepdim`` optional)
+``max_dim`` / ``min_dim`` max / min along a dimension: (values, int64 indices)
 ``segmented_scan``        inclusive segmented sum scan (uint8 heads or int32 bitmask)
 ``sort`` / ``sort_by_key`` stable LSD radix sort, 32- and 64-bit keys (+ 4- / 8-byte values)
 ``argsort``               int64 stable sorting permutation (ascending or descending)
@@ -141,6 +143,48 @@ def _(x, dim):
             torch.empty(x.shape, dtype=torch.int64, device=x.device))
 
 
+def _reduced(x: Tensor, dim: int, keepdim: bool) -> list[int]:
+    d = dim % x.dim()
+    return list(x.shape[:d]) + ([1] if keepdim else []) + list(x.shape[d + 1:])
+
+
+@torch.library.custom_op(f"{NS}::reduce_dim", mutates_args=())
+def reduce_dim(x: Tensor, dim: int, op: str, keepdim: bool = False) -> Tensor:
+    """reduce_dim(Tensor x, int dim, str op, bool keepdim) -> Tensor   (op: "sum", "max", "min" along ``dim``)"""
+    return _scan.reduce(x, op, dim=dim, keepdim=keepdim)
+
+
+@reduce_dim.register_fake
+def _(x, dim, op, keepdim=False):
+    return x.new_empty(_reduced(x, dim, keepdim))
+
+
+@torch.library.custom_op(f"{NS}::max_dim", mutates_args=())
+def max_dim(x: Tensor, dim: int, keepdim: bool = False) -> tuple[Tensor, Tensor]:
+    """max_dim(Tensor x, int dim, bool keepdim) -> (Tensor, Tensor)   (values, int64 indices: ``torch.max(x, dim)``)"""
+    v, i = _scan.reduce(x, "max", dim=dim, keepdim=keepdim, return_indices=True)
+    return v, i
+
+
+@max_dim.register_fake
+def _(x, dim, keepdim=False):
+    shape = _reduced(x, dim, keepdim)
+    return x.new_empty(shape), x.new_empty(shape, dtype=torch.int64)
+
+
+@torch.library.custom_op(f"{NS}::min_dim", mutates_args=())
+def min_dim(x: Tensor, dim: int, keepdim: bool = False) -> tuple[Tensor, Tensor]:
+    """min_dim(Tensor x, int dim, bool keepdim) -> (Tensor, Tensor)   (values, int64 indices: ``torch.min(x, dim)``)"""
+    v, i = _scan.reduce(x, "min", dim=dim, keepdim=keepdim, return_indices=True)
+    return v, i
+
+
+@min_dim.register_fake
+def _(x, dim, keepdim=False):
+    shape = _reduced(x, dim, keepdim)
+    return x.new_empty(shape), x.new_empty(shape, dtype=torch.int64)
+
+
 @torch.library.custom_op(f"{NS}::segmented_scan", mutates_args=())
 def segmented_scan(x: Tensor, flags: Tensor) -> Tensor:
     """segmented_scan(Tensor x, Tensor flags) -> Tensor   (float32 / int64 / float64)"""
@@ -250,7 +294,8 @@ def _(x, flags):
 
 OPS = {
     "heat_step": heat_step, "heat_stepn": heat_stepn, "scan": scan, "scan_op": scan_op,
-    "scan_dim": scan_dim, "cummax": cummax, "cummin": cummin, "segmented_scan": segmented_scan,
+    "scan_dim": scan_dim, "cummax": cummax, "cummin": cummin, "reduce_dim": reduce_dim, "max_dim": max_dim,
+    "min_dim": min_dim, "segmented_scan": segmented_scan,
     "sort": sort, "sort_by_key": sort_by_key, "argsort": argsort, "spmv_csr": spmv_csr, "transpose": transpose, "sgemm": sgemm,
     "gemv": gemv, "copy_if": copy_if,
 }

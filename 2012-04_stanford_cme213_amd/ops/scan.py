@@ -15,7 +15,10 @@
   over the flattened tensor (``csrc/hip/scan_dim_arg.hip``: the same batched
   kernels with a (value, index) carry).
 * :func:`reduce` -- sum / max / min; the lecture's shared-memory tree
-  (``slides/Lecture05.pdf`` 15-16) as ``algo="tree"``.
+  (``slides/Lecture05.pdf`` 15-16) as ``algo="tree"``. With ``dim=`` /
+  ``keepdim`` / ``return_indices`` it reduces along one dimension of a tensor
+  of any rank, every scan dtype (``csrc/hip/reduce_dim.hip``), as do
+  :func:`argmax` / :func:`argmin`; :func:`reduce_dim_launch_info`.
 * Both take float32 / int32 and int64 / float64 (``scan`` also uint32); the
   64-bit kernels are ``csrc/hip/scan64.hip`` (``algo="rts"`` / ``"lookback"``
   only; everything else here is 32-bit).
@@ -688,13 +691,117 @@ def summed_area_table(x: torch.Tensor, out: torch.Tensor | None = None) -> torch
     return scan(out, out=out, dim=-2)
 
 
-def reduce(x: torch.Tensor, op: str = "sum", algo: str = "vector") -> torch.Tensor:
-    """Full reduction (``op``: "sum", "max", "min") of a float32/int32/int64/
-    float64 tensor; returns a 0-d tensor on x's device. An int64 sum wraps
-    modulo 2^64. ``algo="tree"`` (the lecture's LDS tree, sum only) is 32-bit
-    only and raises a ``TypeError`` for 64-bit input. int32 sums wrap modulo
-    2^32 on both backends. A 32-bit view that is not 16-byte aligned is copied
-    for ``algo="vector"`` on the GPU."""
+_ext.proto(_ext.HIP_PROTOS, "cme_reduce_dim", "pppqqqiipp")
+_ext.proto(_ext.HIP_PROTOS, "cme_reduce_dim_info", "qqqiiip")
+_ext.proto(_ext.HIP_PROTOS, "cme_reduce_dim_ws_bytes", "qqqiip")
+_ext.proto(_ext.CPU_PROTOS, "cme_cpu_reduce_dim", "pppqqqii")
+
+ReduceWithIndices = collections.namedtuple("ReduceWithIndices", ["values", "indices"])
+
+
+def _reduce_split(shape, dim: int | None) -> tuple[int, int, int, int | None]:
+    """(outer, n, inner, d) of reducing ``shape`` along ``dim`` (``d``: the
+    non-negative dimension); the flattened tensor for ``dim=None`` (``d`` None)."""
+    if dim is None:
+        n = 1
+        for s in shape:
+            n *= int(s)
+        return 1, n, 1, None
+    try:
+        outer, n, inner = _split_dim(shape, dim)
+    except (ValueError, IndexError) as e:
+        raise type(e)(str(e).replace("scan:", "reduce:")) from None
+    return outer, n, inner, dim % len(shape)
+
+
+def _reduced_shape(shape, d: int | None, keepdim: bool) -> tuple:
+    shape = tuple(int(s) for s in shape)
+    if d is None:
+        return (1,) * len(shape) if keepdim else ()
+    return shape[:d] + ((1,) if keepdim else ()) + shape[d + 1:]
+
+
+def _reduce_dim(x: torch.Tensor, op: str, dim: int | None, keepdim: bool, indices: bool):
+    """The reduction of ``x`` along ``dim`` (``None``: of the flattened
+    tensor), seen as ``(outer, n, inner)`` like :func:`_scan_dim`; the kernels
+    of ``csrc/hip/reduce_dim.hip`` under the launch plan of the scans along a
+    dimension (:func:`reduce_dim_launch_info`), ``cme_cpu_reduce_dim`` on CPU
+    tensors. Returns ``(values, indices)``, ``indices`` None unless asked for.
+    Neither synchronises."""
+    if op not in _OPS:
+        raise ValueError(f"reduce: op {op!r} is not one of {sorted(_OPS)}")
+    if indices and op == "sum":
+        raise ValueError("reduce: return_indices is for op='max' / 'min'; a sum has no index")
+    if x.dtype not in _DT64 and x.dtype not in _DT_SCAN:
+        raise TypeError(f"reduce: {x.dtype} is not supported along a dimension")
+    code = _dtype_code(x.dtype)
+    outer, n, inner, d = _reduce_split(x.shape, dim)
+    shape = _reduced_shape(x.shape, d, keepdim)
+    if n == 0:
+        if op != "sum":
+            raise ValueError(f"reduce: {op} of an empty dimension has no value")
+        return torch.zeros(shape, dtype=x.dtype, device=x.device), None
+    if not x.is_contiguous():
+        x = x.contiguous()
+    vout = torch.empty(shape, dtype=x.dtype, device=x.device)
+    iout = torch.empty(shape, dtype=torch.int64, device=x.device) if indices else None
+    if outer == 0 or inner == 0:
+        return vout, iout
+    iptr = None if iout is None else iout.data_ptr()
+    if not x.is_cuda:
+        _ext.call_cpu("cme_cpu_reduce_dim", x.data_ptr(), vout.data_ptr(), iptr, outer, n, inner, code, _OPS[op])
+        return vout, iout
+    import ctypes
+
+    nbytes = ctypes.c_longlong(0)
+    with torch.cuda.device(x.device):
+        _ext.call_hip("cme_reduce_dim_ws_bytes", outer, n, inner, code, int(indices), ctypes.addressof(nbytes))
+        ws = _dim_ws(x.device, nbytes.value, "reduce_arg_dim" if indices else "reduce_dim")
+        _ext.call_hip("cme_reduce_dim", x.data_ptr(), vout.data_ptr(), iptr, outer, n, inner, code, _OPS[op],
+                      None if ws is None else ws.data_ptr(), _ext.stream_ptr(x.device))
+    return vout, iout
+
+
+def reduce(x: torch.Tensor, op: str = "sum", algo: str = "vector", dim: int | None = None, keepdim: bool = False,
+           return_indices: bool = False):
+    """Reduction (``op``: "sum", "max", "min").
+
+    Without ``dim``, ``keepdim`` and ``return_indices``: the full reduction of
+    a float32/int32/int64/float64 tensor; returns a 0-d tensor on x's device.
+    An int64 sum wraps modulo 2^64. ``algo="tree"`` (the lecture's LDS tree,
+    sum only) is 32-bit only and raises a ``TypeError`` for 64-bit input. int32
+    sums wrap modulo 2^32 on both backends. A 32-bit view that is not 16-byte
+    aligned is copied for ``algo="vector"`` on the GPU.
+
+    With any of the three: the reduction along dimension ``dim`` (one int,
+    negative allowed; ``None``: the flattened tensor) of a tensor of any rank
+    and any scan dtype (float32, int32, uint32, int64, float64), by
+    ``csrc/hip/reduce_dim.hip`` / ``cme_cpu_reduce_dim``; ``algo`` must stay at
+    its default. ``keepdim`` keeps the reduced dimension with size 1 (every
+    dimension for ``dim=None``). The rules, the same on both backends:
+
+    * "sum" keeps ``x``'s dtype (no promotion); integers wrap. A float sum is a
+      tree fixed by the launch shape and the operand's 16-byte phase: two runs
+      of one call are bitwise equal. An empty dimension sums to zero.
+    * "max" / "min" are the IEEE 754-2019 maximum / minimum: a NaN in the line
+      gives NaN, ``max(+0.0, -0.0)`` is ``+0.0`` and ``min`` is ``-0.0``. An
+      empty dimension raises ``ValueError``.
+    * ``return_indices=True`` ("max" / "min" only) returns the named pair
+      ``(values, indices)`` of ``torch.max(x, dim)`` / ``torch.min(x, dim)`` on
+      CPU tensors: the index (int64, along ``dim``, or in the flattened tensor)
+      of the first NaN if the line has one, else of the first element equal to
+      the extreme; ``values`` is ``x`` at that index, bit for bit.
+
+    The chunk partials of a launch that splits ``n`` live in buffers of their
+    own ("reduce_dim" / "reduce_arg_dim" families of :func:`_dim_ws`), so under
+    stream capture the rule of the scans holds: run the call once before
+    capturing it."""
+    if dim is not None or keepdim or return_indices:
+        if algo != "vector":
+            raise TypeError(f"reduce: algo {algo!r} is for the flattened reduction; with dim, keepdim or "
+                            "return_indices, algo stays at its default")
+        v, i = _reduce_dim(x, op, dim, keepdim, return_indices)
+        return ReduceWithIndices(v, i) if return_indices else v
     x = x.contiguous()
     wide = x.dtype in _DT64
     if wide and algo != "vector":
@@ -710,6 +817,49 @@ def reduce(x: torch.Tensor, op: str = "sum", algo: str = "vector") -> torch.Tens
     else:
         _ext.call_cpu("cme_cpu_reduce", x.data_ptr(), x.numel(), dt, _OPS[op], out.data_ptr())
     return out
+
+
+def argmax(x: torch.Tensor, dim: int | None = None, keepdim: bool = False) -> torch.Tensor:
+    """``torch.argmax(x, dim, keepdim)``: the ``indices`` of
+    ``reduce(x, "max", dim=dim, keepdim=keepdim, return_indices=True)``, an
+    int64 tensor on ``x``'s device. No host synchronisation."""
+    return _reduce_dim(x, "max", dim, keepdim, True)[1]
+
+
+def argmin(x: torch.Tensor, dim: int | None = None, keepdim: bool = False) -> torch.Tensor:
+    """``torch.argmin(x, dim, keepdim)``; see :func:`argmax`."""
+    return _reduce_dim(x, "min", dim, keepdim, True)[1]
+
+
+def reduce_dim_launch_info(shape, dim: int | None, dtype: torch.dtype = torch.float32, op: str = "sum",
+                           device: torch.device | str = "cuda", indices: bool = False) -> dict:
+    """How ``reduce(x, op, dim=dim)`` of a 16-byte aligned tensor of ``shape``
+    runs on ``device``: the keys of :func:`scan_dim_launch_info`, from the same
+    plan. ``form`` "flat" (a single line, ``dim=None`` included) runs as a row
+    chunked across the device; ``workgroups`` is the grid of the reduce pass,
+    and ``ws_bytes`` holds one partial per (line, chunk) when ``chunks > 1``
+    (with ``indices=True``, where the default "sum" is read as "max", an int64
+    index beside every value). The CPU backend reports the shape split only."""
+    import ctypes
+
+    if op not in _OPS:
+        raise ValueError(f"reduce: op {op!r} is not one of {sorted(_OPS)}")
+    if indices and op == "sum":
+        op = "max"
+    outer, n, inner, _ = _reduce_split(tuple(shape), dim)
+    code = _dtype_code(dtype)
+    form = 0 if outer == 1 and inner == 1 else 1 if inner == 1 else 2
+    d = {"form": _DIM_FORMS[form], "outer": outer, "n": n, "inner": inner, "chunks": 1, "chunk": n, "tile": 0,
+         "vector": 1, "waves": 0, "workgroups": 0, "ws_bytes": 0}
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        return d
+    info = (ctypes.c_longlong * 8)()
+    with torch.cuda.device(dev):
+        _ext.call_hip("cme_reduce_dim_info", outer, n, inner, code, _OPS[op], int(indices), ctypes.addressof(info))
+    d.update(form=_DIM_FORMS[int(info[0])], chunks=int(info[1]), chunk=int(info[2]), tile=int(info[3]),
+             vector=int(info[4]), workgroups=int(info[5]), ws_bytes=int(info[6]), waves=int(info[7]))
+    return d
 
 
 def head_flags_from_offsets(s: torch.Tensor, n: int, device=None, bitmask: bool = True) -> torch.Tensor:

@@ -16,6 +16,9 @@ per measurement with the reference number it is compared against.
   scan_arg   cummax with indices along a dimension and flattened, float32 / int64,
              against the values-only scan, torch.cummax and the copy of the same
              run (profiles/scan_cumarg.md)
+  reduce_dim sum / max / max with indices along one dimension, one shape per
+             regime, float32 / int64, against torch.sum / amax / max(x, dim) and
+             the flattened reduce of the same run (profiles/reduce_dim.md)
   spmvscan   the 15 final-project shapes (BASELINE #19-21, synthetic values)
   cipher     19.76 MB moby-dick x16 (BASELINE #1-3)
   pagerank   2^21 nodes, avg 8 edges, 20 iterations (BASELINE #5)
@@ -305,6 +308,52 @@ def main():
                          GBps=round((2 * size + (0 if name in ("copy", "scan_dim-max") else 8)) * n / ms / 1e6, 1),
                          **extra)
                 del xs, ys, idx, arms
+
+    if want("reduce_dim"):
+        # Reductions along one dimension (csrc/hip/reduce_dim.hip), one shape per
+        # regime of the scan_dim table: sum, max, and max with indices against
+        # torch.sum / torch.amax / torch.max(x, dim), and against the flattened
+        # reduce of this project over the same bytes -- the read-rate yardstick
+        # of the same run. Measured like scan_dim: three operand sets, arms
+        # alternated and reshuffled, an event pair per call. `read_share`: the
+        # yardstick's time over the arm's; `vs_torch`: torch's time over ours.
+        shapes = [((65536, 2048), -1, "row, K == 1"), ((1 << 20, 64), -1, "row, short rows"),
+                  ((16, 1 << 22), -1, "row, K > 1"), ((1 << 27,), 0, "one line"), ((8192, 8192), 0, "column, wide"),
+                  ((1 << 21, 64), 0, "column, tall and thin, K > 1"), ((64, 1 << 21), 0, "column, short and wide"),
+                  ((256, 512, 512), 1, "column"), ((1 << 22, 3), 0, "column, narrow")]
+        for dt in (torch.float32, torch.int64):
+            for shape, dim, regime in shapes:
+                if dt == torch.int64:
+                    xs = [torch.randint(-2 ** 40, 2 ** 40, shape, device=dev, dtype=dt) for _ in range(3)]
+                else:
+                    xs = [torch.rand(shape, device=dev, dtype=dt) for _ in range(3)]
+                pairs = {"reduce_dim-sum": "torch.sum", "reduce_dim-max": "torch.amax",
+                         "reduce_dim-max+indices": "torch.max"}
+                arms = {
+                    "reduce-flat": lambda k: sc.reduce(xs[k].view(-1), "sum"),
+                    "reduce_dim-sum": lambda k: sc.reduce(xs[k], "sum", dim=dim),
+                    "torch.sum": lambda k: torch.sum(xs[k], dim),
+                    "reduce_dim-max": lambda k: sc.reduce(xs[k], "max", dim=dim),
+                    "torch.amax": lambda k: torch.amax(xs[k], dim),
+                    "reduce_dim-max+indices": lambda k: sc.reduce(xs[k], "max", dim=dim, return_indices=True),
+                    "torch.max": lambda k: torch.max(xs[k], dim),
+                }
+                res = alternate(arms, rounds=8)
+                size, n = xs[0].element_size(), xs[0].numel()
+                flat_ms = res["reduce-flat"][0]
+                for name, (ms, lo, hi) in res.items():
+                    extra = {}
+                    if name in pairs:
+                        info = sc.reduce_dim_launch_info(shape, dim, dtype=dt, op="max", device=dev,
+                                                         indices=name.endswith("indices"))
+                        t_ms, t_lo, t_hi = res[pairs[name]]
+                        extra = dict(form=info["form"], chunks=info["chunks"], vector=info["vector"], waves=info["waves"],
+                                     workgroups=info["workgroups"], ws_bytes=info["ws_bytes"], torch_ms=round(t_ms, 4),
+                                     vs_torch=round(t_ms / ms, 2), spread_ms=round(max(hi - lo, t_hi - t_lo), 4))
+                    emit(bench="reduce_dim", dtype=str(dt).split(".")[1], shape=list(shape), dim=dim, regime=regime,
+                         arm=name, ms=round(ms, 4), ms_min=round(lo, 4), ms_max=round(hi, 4),
+                         GBps=round(size * n / ms / 1e6, 1), read_share=round(flat_ms / ms, 3), **extra)
+                del xs, arms
 
     if want("spmvscan"):
         from cme213x.models.spmv_scan import BENCH_SHAPES, REF_MS, SpmvScanSolver, generate
