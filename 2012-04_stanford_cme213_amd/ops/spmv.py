@@ -215,7 +215,7 @@ def to_ell(a: CSR, K: int | None = None, max_entries: int = 1 << 27) -> tuple[EL
     the returned COO remainder (empty when K >= max row length)."""
     rp = a.rp.cpu().numpy().astype(np.int64)
     lens = np.diff(rp)
-    K = int(lens.max()) if K is None else int(K)
+    K = (int(lens.max()) if lens.size else 0) if K is None else int(K)
     if K * a.nrows > max_entries:
         raise ValueError(f"ELL width {K} x {a.nrows} rows exceeds {max_entries} entries: use HYB")
     rows = _row_ids(a)
@@ -238,6 +238,8 @@ def hyb_k(a: CSR) -> int:
     """Bell & Garland's ELL width: the largest K such that at least
     max(4096, nrows/3) rows have >= K nonzeros."""
     lens = np.diff(a.rp.cpu().numpy().astype(np.int64))
+    if lens.size == 0:
+        return 0
     need = max(4096, a.nrows // 3)
     hist = np.bincount(lens)
     rows_ge = np.cumsum(hist[::-1])[::-1]  # rows_ge[k] = #rows with len >= k
@@ -403,17 +405,61 @@ def _auto_max_row(a: CSR) -> int:
     return v
 
 
+def _first_tensor(a) -> torch.Tensor:
+    """One of the matrix's own tensors (its device is the matrix's)."""
+    if isinstance(a, HYB):
+        return a.ell.col
+    if isinstance(a, CSRColBlocked):
+        return a.blocks[0].rp
+    for name in ("rp", "col", "data", "row"):
+        if hasattr(a, name):
+            return getattr(a, name)
+    raise TypeError(type(a))
+
+
+def _check_operands(a, x: torch.Tensor, y: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The operand checks of :func:`spmv` (the kernels only see raw
+    pointers): x is a float32 vector of ncols entries on the matrix's device
+    (made contiguous if it is not); y, when given, a contiguous float32
+    vector of nrows entries on the same device -- it is written in place, so
+    it cannot be copied. Wrong dtype: TypeError; anything else: ValueError."""
+    nrows, ncols = (a.ell.nrows, a.ell.ncols) if isinstance(a, HYB) else (a.nrows, a.ncols)
+    dev = _first_tensor(a).device
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise TypeError(f"spmv: x must be a float32 tensor, not {getattr(x, 'dtype', type(x))}")
+    if x.dim() != 1 or x.numel() != ncols:
+        raise ValueError(f"spmv: x must be a vector of ncols = {ncols} entries, not {tuple(x.shape)}")
+    if x.device != dev:
+        raise ValueError(f"spmv: x is on {x.device}, the matrix on {dev}")
+    if y is None:
+        return x.contiguous(), torch.zeros(nrows, dtype=torch.float32, device=dev)
+    if not isinstance(y, torch.Tensor) or y.dtype != torch.float32:
+        raise TypeError(f"spmv: y must be a float32 tensor, not {getattr(y, 'dtype', type(y))}")
+    if y.dim() != 1 or y.numel() != nrows:
+        raise ValueError(f"spmv: y must be a vector of nrows = {nrows} entries, not {tuple(y.shape)}")
+    if y.device != dev:
+        raise ValueError(f"spmv: y is on {y.device}, the matrix on {dev}")
+    if not y.is_contiguous():
+        raise ValueError("spmv: y is written in place and must be contiguous")
+    return x.contiguous(), y
+
+
+def _aligned16(*ts: torch.Tensor) -> bool:
+    return all(t.data_ptr() % 16 == 0 for t in ts)
+
+
 def spmv(a, x: torch.Tensor, y: torch.Tensor | None = None, kernel: str = "auto", beta: float = 0.0) -> torch.Tensor:
     """y = A x + beta*y for any of the formats. ``kernel`` (CSR only):
     "scalar", "vector", "stream" (CSR-stream: row blocks staged through LDS),
     "short" (a lane per row, the first 8 entries of a row as one batch of loads),
     or "auto" (scalar for short regular rows -- mean <= 8, longest <= 16 --,
     stream for a mean row length below 32, where CSR-vector idles most of its
-    lanes; vector with auto group above). To pick the FORMAT by
-    the matrix structure, convert once with :func:`prepare`."""
-    if y is None:
-        nrows = a.ell.nrows if isinstance(a, HYB) else a.nrows
-        y = torch.zeros(nrows, dtype=torch.float32, device=x.device)
+    lanes; vector with auto group above). CSR-stream reads col / val in 16-byte
+    pieces: a CSR whose col or val does not start on a 16-byte boundary (an
+    offset view) takes CSR-vector in its place. To pick the FORMAT by
+    the matrix structure, convert once with :func:`prepare`. ``x`` and ``y``
+    are checked (:func:`_check_operands`); ``beta == 0`` overwrites ``y``."""
+    x, y = _check_operands(a, x, y)
     if not x.is_cuda:
         if not isinstance(a, CSR):
             raise TypeError("CPU path supports CSR only")
@@ -439,8 +485,8 @@ def spmv(a, x: torch.Tensor, y: torch.Tensor | None = None, kernel: str = "auto"
     elif isinstance(a, CSR) and kernel == "short":
         _ext.call_hip("cme_spmv_csr_short", a.nrows, a.rp.data_ptr(), a.col.data_ptr(), a.val.data_ptr(),
                       x.data_ptr(), y.data_ptr(), short_rows_per_lane(a), float(beta), s)
-    elif isinstance(a, CSR) and (kernel == "stream" or
-                                 (kernel == "auto" and a.nnz < STREAM_MAX_MEAN * max(1, a.nrows))):
+    elif isinstance(a, CSR) and _aligned16(a.col, a.val) and \
+            (kernel == "stream" or (kernel == "auto" and a.nnz < STREAM_MAX_MEAN * max(1, a.nrows))):
         _ext.call_hip("cme_spmv_csr_stream", a.nrows, a.rp.data_ptr(), a.col.data_ptr(), a.val.data_ptr(),
                       x.data_ptr(), y.data_ptr(), stream_rows(a), float(beta), s)
     elif isinstance(a, CSR):

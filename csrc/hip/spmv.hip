@@ -509,6 +509,7 @@ CME_EXPORT int cme_spmv_halo(int nb, const int* rows, const int* rp, const int* 
 CME_EXPORT int cme_spmv_csr(int nrows, const int* rp, const int* col, const float* val, const float* x, float* y,
                             int group, float beta, void* stream) {
     hipStream_t s = as_stream(stream);
+    if (nrows <= 0) return 0;
     switch (group) {
         case 1: hipLaunchKernelGGL(csr_scalar_kernel, dim3(cdiv(nrows, 256)), dim3(256), 0, s, nrows, rp, col, val, x, y, beta); break;
 #define V(G) case G: hipLaunchKernelGGL(csr_vector_kernel<G>, dim3(cdiv((size_t)nrows * G, 256)), dim3(256), 0, s, nrows, rp, col, val, x, y, beta); break;
@@ -519,11 +520,15 @@ CME_EXPORT int cme_spmv_csr(int nrows, const int* rp, const int* col, const floa
     CME_LAUNCH_STATUS();
 }
 
-// CSR-stream: rows_per_block 64 / 128 / 256 / 512 (the host picks it from the mean
-// row length: csr_stream_kernel).
+// CSR-stream: rows_per_block 64 / 128 / 256 / 512 / 1024 (the host picks it from the
+// mean row length: csr_stream_kernel). The kernel reads the aligned body of a
+// block's range as 16-B pieces at col + a0, a0 % 4 == 0: col and val must be
+// 16-B aligned themselves (an offset view is refused; spmv() sends it to
+// CSR-vector).
 CME_EXPORT int cme_spmv_csr_stream(int nrows, const int* rp, const int* col, const float* val, const float* x,
                                    float* y, int rows_per_block, float beta, void* stream) {
     hipStream_t s = as_stream(stream);
+    if (((uintptr_t)col % 16) || ((uintptr_t)val % 16)) return (int)hipErrorInvalidValue;
     if (nrows <= 0) return 0;
     switch (rows_per_block) {
 #define V(R) case R: hipLaunchKernelGGL(csr_stream_kernel<R>, dim3(cdiv(nrows, R)), dim3(256), 0, s, nrows, rp, col, val, x, y, beta); break;
@@ -563,6 +568,7 @@ CME_EXPORT int cme_spmv_csr_aligned(int nrows, long long nnz, const int* rp, con
                                     const float* x, float* y, int group, float beta, void* stream) {
     hipStream_t s = as_stream(stream);
     if (((uintptr_t)col % 16) || ((uintptr_t)val % 16)) return (int)hipErrorInvalidValue;
+    if (nrows <= 0) return 0;
     // CME_SPMV_NT: 0 plain stream loads, 1 non-temporal, 2 (default) non-temporal
     // only when the col/val stream cannot stay in the 256 MB Infinity Cache
     // between calls. Measured (profiles/spmv_nt_r4.md): non-temporal wins cold
@@ -590,6 +596,7 @@ CME_EXPORT int cme_spmv_csr_aligned(int nrows, long long nnz, const int* rp, con
 
 CME_EXPORT int cme_spmv_ell(int nrows, int K, const int* col, const float* val, const float* x, float* y, float beta,
                             void* stream) {
+    if (nrows <= 0) return 0;
     hipLaunchKernelGGL(ell_kernel, dim3(cdiv(nrows, 256)), dim3(256), 0, as_stream(stream), nrows, K, col, val, x, y,
                        beta);
     CME_LAUNCH_STATUS();
@@ -600,9 +607,13 @@ CME_EXPORT int cme_spmv_dia(int nrows, int ncols, int ndiag, const int* offsets,
     // 4 rows per lane only when that still leaves >= 1M lanes (16 waves per
     // SIMD): with 1M rows its 250K lanes lose to the one-row kernel (27-point
     // Laplacian 41 vs 30 us, 5-point 11.0 vs 10.2 us; 16M-row 5-point 99 vs
-    // 117 us -- profiles/spmv_r2.md). CME_SPMV_DIA1 forces the one-row kernel.
-    const bool one_row = cme::tune_get(cme::kTuneSpmvDia1) != 0;
-    if (nrows % 4 == 0 && nrows >= (4 << 20) && !one_row) {
+    // 117 us -- profiles/spmv_r2.md). CME_SPMV_DIA1: 0 by that rule, 2 forces
+    // the four-row kernel wherever it applies (nrows % 4 == 0, data and y 16-B
+    // aligned for its 16-B accesses), any other value forces the one-row kernel.
+    if (nrows <= 0) return 0;
+    const long mode = cme::tune_get(cme::kTuneSpmvDia1);
+    const bool four_ok = nrows % 4 == 0 && (uintptr_t)data % 16 == 0 && (uintptr_t)y % 16 == 0;
+    if (four_ok && (mode == 2 || (mode == 0 && nrows >= (4 << 20)))) {
         hipLaunchKernelGGL(dia4_kernel, dim3(cdiv(nrows / 4, 256)), dim3(256), 0, as_stream(stream), nrows, ncols,
                            ndiag, offsets, data, x, y, beta);
         CME_LAUNCH_STATUS();
@@ -616,6 +627,7 @@ CME_EXPORT int cme_spmv_dia(int nrows, int ncols, int ndiag, const int* offsets,
 CME_EXPORT int cme_spmv_coo(int nrows, long long nnz, const int* row, const int* col, const float* val, const float* x,
                             float* y, float beta, int accumulate, void* stream) {
     hipStream_t s = as_stream(stream);
+    if (nrows <= 0) return 0;
     if (!accumulate) hipLaunchKernelGGL(scale_kernel, dim3(cdiv(nrows, 256)), dim3(256), 0, s, y, nrows, beta);
     if (nnz > 0) {
         const long long waves = (nnz + 255) / 256;

@@ -31,7 +31,7 @@ enum TuneKey : int {
     kTuneStreamNCapPct,    // CME_STREAMN_CAPPCT
     kTuneSpmvScanMulti,    // CME_SPMVSCAN_MULTI
     kTuneSpmvNT,           // CME_SPMV_NT: aligned-CSR stream loads (0 plain, 1 non-temporal, 2 by size)
-    kTuneSpmvDia1,         // CME_SPMV_DIA1
+    kTuneSpmvDia1,         // CME_SPMV_DIA1: DIA kernel (0 by row count, 1 one row per lane, 2 four rows per lane where nrows % 4 == 0)
     kTunePipeTaper,        // CME_PIPE_TAPER: half-height last chunks per strip of a multi-round pass (0 off, -1 auto)
     kTuneRadixUpUnr,       // CME_RADIX_UP_UNR: radix upsweep 16-B loads in flight per lane (4, 8, 16)
     kTuneRadixOsLanes,     // CME_RADIX_OS_LANES: onesweep ranks, 1 lane order where the probe passed, 0 ballot match
