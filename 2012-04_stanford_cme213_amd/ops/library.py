@@ -22,6 +22,7 @@ Ops (schema in each docstring; "!" = mutated in place):
 ``segmented_scan``        inclusive segmented sum scan (uint8 heads or int32 bitmask)
 ``sort`` / ``sort_by_key`` stable LSD radix sort, 32- and 64-bit keys (+ 4- / 8-byte values)
 ``argsort``               int64 stable sorting permutation (ascending or descending)
+``sort_dim``              stable sort along a dimension: (values, int64 indices)
 ``spmv_csr``              y = A x, A in CSR (rp, col, val)
 ``transpose``             2-D fp32 transpose
 ``sgemm`` / ``gemv``      C = A B (MFMA), y = A x
@@ -233,6 +234,20 @@ def _(keys, descending=False):
     return torch.empty(keys.shape, dtype=torch.int64, device=keys.device)
 
 
+@torch.library.custom_op(f"{NS}::sort_dim", mutates_args=())
+def sort_dim(x: Tensor, dim: int, descending: bool = False) -> tuple[Tensor, Tensor]:
+    """sort_dim(Tensor x, int dim, bool descending=False) -> (Tensor, Tensor)
+    (values, int64 indices along ``dim``: ``torch.sort(x, dim, descending, stable=True)``)"""
+    v, i = _sort.sort(x, dim=dim, descending=descending)
+    return _fresh(v, x), i
+
+
+@sort_dim.register_fake
+def _(x, dim, descending=False):
+    return (torch.empty_like(x, memory_format=torch.contiguous_format),
+            torch.empty(x.shape, dtype=torch.int64, device=x.device))
+
+
 # ------------------------------------------------------------------ sparse / dense linear algebra
 @torch.library.custom_op(f"{NS}::spmv_csr", mutates_args=())
 def spmv_csr(rp: Tensor, col: Tensor, val: Tensor, x: Tensor, ncols: int) -> Tensor:
@@ -296,6 +311,6 @@ OPS = {
     "heat_step": heat_step, "heat_stepn": heat_stepn, "scan": scan, "scan_op": scan_op,
     "scan_dim": scan_dim, "cummax": cummax, "cummin": cummin, "reduce_dim": reduce_dim, "max_dim": max_dim,
     "min_dim": min_dim, "segmented_scan": segmented_scan,
-    "sort": sort, "sort_by_key": sort_by_key, "argsort": argsort, "spmv_csr": spmv_csr, "transpose": transpose, "sgemm": sgemm,
+    "sort": sort, "sort_by_key": sort_by_key, "argsort": argsort, "sort_dim": sort_dim, "spmv_csr": spmv_csr, "transpose": transpose, "sgemm": sgemm,
     "gemv": gemv, "copy_if": copy_if,
 }

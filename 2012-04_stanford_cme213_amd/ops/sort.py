@@ -17,8 +17,16 @@ upsweep + one-launch count scan + downsweep per 8-bit digit), "onesweep"
 one write of the keys per digit with decoupled look-back across tiles). Both
 are stable and exact; reduce-then-scan is the default because it measures
 faster on MI355X (16M keys: profiles/sort_r3.md).
+
+``sort(x, dim=d)`` / ``argsort(x, dim=d)`` sort every line of a tensor of any
+rank along one dimension and return ``(values, indices)``: a batched LDS radix
+sort packing several short lines into one workgroup's tile
+(``csrc/hip/sort_dim.hip``), the two 1-D key-value sorts composed for lines
+above the tile, ``cme_cpu_sort_dim`` on the CPU.
 """
 from __future__ import annotations
+
+import collections
 
 import torch
 
@@ -38,6 +46,11 @@ _ext.proto(_ext.CPU_PROTOS, "cme_cpu_radix_sort_kv_u32", "ppppqii")
 _ext.proto(_ext.HIP_PROTOS, "cme_radix_sort64", "ppppppqiiiipp")
 _ext.proto(_ext.HIP_PROTOS, "cme_radix_sort64_tile", "")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_radix_sort_kv_u64", "ppppqiii")
+_ext.proto(_ext.HIP_PROTOS, "cme_sort_dim", "pppqqqiip")
+_ext.proto(_ext.HIP_PROTOS, "cme_sort_dim_info", "qqqip")
+_ext.proto(_ext.CPU_PROTOS, "cme_cpu_sort_dim", "pppqqqii")
+
+SortWithIndices = collections.namedtuple("SortWithIndices", ["values", "indices"])
 
 _MIN32 = -(2 ** 31)
 _MIN64 = -(2 ** 63)
@@ -308,8 +321,126 @@ def _workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
     return t
 
 
+_DT_SORT_DIM = {torch.uint32: 0, torch.int32: 1, torch.float32: 2, torch.uint64: 3, torch.int64: 4, torch.float64: 5}
+_SORT_DIM_FORMS = ("flat", "row", "col")
+_SORT_DIM_REGIMES = ("tile", "composed")
+# bit patterns move through the tensor ops of the composed regime as signed integers
+_SIGNED = {torch.uint32: torch.int32, torch.float32: torch.int32, torch.int32: torch.int32,
+           torch.uint64: torch.int64, torch.float64: torch.int64, torch.int64: torch.int64}
+
+
+def _sort_split(shape, dim: int) -> tuple[int, int, int]:
+    from .scan import _split_dim
+
+    try:
+        return _split_dim(shape, dim)
+    except (ValueError, IndexError) as e:
+        raise type(e)(str(e).replace("scan:", "sort:")) from None
+
+
+def _sort_dim_info(outer: int, n: int, inner: int, code: int, device: torch.device) -> list[int]:
+    import ctypes
+
+    info = (ctypes.c_longlong * 8)()
+    with torch.cuda.device(device):
+        _ext.call_hip("cme_sort_dim_info", outer, n, inner, code, ctypes.addressof(info))
+    return [int(v) for v in info]
+
+
+def _sort_dim_composed(x: torch.Tensor, outer: int, n: int, inner: int, descending: bool):
+    """Lines longer than the tile kernel takes, from the 1-D sorts: a stable
+    key-value sort of every key carrying its flat position, then a stable
+    key-value sort of those positions by their line number (plain unsigned
+    keys of ``bit_length(lines - 1)`` bits), which leaves every line's keys
+    together and in sorted order; ``values`` is ``x`` gathered at that
+    permutation, ``indices`` its position along the dimension. The line
+    numbers, the gather and the index split are tensor ops."""
+    total = outer * n * inner
+    if total >= 1 << 32:
+        raise ValueError("sort: dim= with lines above the tile kernel's length takes fewer than 2**32 elements")
+    flat = x.reshape(-1)
+    dev = x.device
+    if total < 1 << 31:
+        pos = torch.arange(total, dtype=torch.int32, device=dev)
+    else:  # positions from 2**31 wrap into the sign bit and are unwrapped below
+        pos = torch.arange(total, dtype=torch.int64, device=dev).to(torch.int32)
+    perm = sort(flat, pos, descending=descending)[1]
+
+    def wide(p):
+        p = p.to(torch.int64)
+        return p if total < 1 << 31 else p & 0xFFFFFFFF
+
+    lines = outer * inner
+    if lines > 1:
+        p = wide(perm)
+        line = ((p // (n * inner)) * inner + p % inner).to(torch.int32)  # lines < 2**32 / n
+        perm = sort(line, perm, key_bits=max(1, (lines - 1).bit_length()))[1]
+    p = wide(perm).view(outer, inner, n).transpose(1, 2).contiguous()  # [o, r, i]: the r-th key of line (o, i)
+    values = flat.view(_SIGNED[x.dtype])[p].view(x.dtype).view(x.shape)
+    indices = ((p // inner) % n).view(x.shape)
+    return values, indices
+
+
+def _sort_dim(x: torch.Tensor, dim: int, descending: bool):
+    """``(values, indices)`` of the stable sort of ``x`` along ``dim``; see
+    :func:`sort`. The tensor is seen as ``(outer, n, inner)`` like the scans
+    along a dimension. GPU: ``csrc/hip/sort_dim.hip`` where a line fits the
+    kernel's tile (:func:`sort_dim_launch_info`), :func:`_sort_dim_composed`
+    above it; CPU: ``cme_cpu_sort_dim``. Neither synchronises."""
+    outer, n, inner = _sort_split(x.shape, dim)
+    if x.dtype not in _DT_SORT_DIM:
+        raise TypeError(f"unsupported key dtype {x.dtype}")
+    code = _DT_SORT_DIM[x.dtype]
+    if not x.is_contiguous():
+        x = x.contiguous()
+    if x.numel() == 0 or n == 1:
+        return x.clone(), torch.zeros(x.shape, dtype=torch.int64, device=x.device)
+    if x.is_cuda and _sort_dim_info(outer, n, inner, code, x.device)[1] == 1:
+        return _sort_dim_composed(x, outer, n, inner, descending)
+    values = torch.empty_like(x)
+    indices = torch.empty(x.shape, dtype=torch.int64, device=x.device)
+    if x.is_cuda:
+        with torch.cuda.device(x.device):
+            _ext.call_hip("cme_sort_dim", x.data_ptr(), values.data_ptr(), indices.data_ptr(), outer, n, inner, code,
+                          int(descending), _ext.stream_ptr(x.device))
+    else:
+        _ext.call_cpu("cme_cpu_sort_dim", x.data_ptr(), values.data_ptr(), indices.data_ptr(), outer, n, inner, code,
+                      int(descending))
+    return values, indices
+
+
+def _check_dim_args(values, algo, num_bits, key_bits) -> None:
+    if values is not None or algo != "radix" or num_bits != 8 or key_bits is not None:
+        raise TypeError("sort: with dim=, the returned indices replace carried values, and algo, num_bits and "
+                        "key_bits stay at their defaults")
+
+
+def sort_dim_launch_info(shape, dim: int, dtype: torch.dtype = torch.float32,
+                         device: torch.device | str = "cuda") -> dict:
+    """How ``sort(x, dim=dim)`` of a tensor of ``shape`` runs on ``device``:
+    ``form`` ("flat": a single line, "row": along the last dimension, "col"),
+    the shape split ``outer`` / ``n`` / ``inner``, ``regime`` ("tile": the LDS
+    kernel, "composed": from the 1-D sorts), ``tile`` (the longest line the
+    kernel takes), ``lines_per_tile``, ``passes`` (digit passes, the line pass
+    included), ``workgroups``, ``items`` (slots per lane) and ``threads``.
+    The CPU backend reports the shape split only."""
+    outer, n, inner = _sort_split(tuple(shape), dim)
+    if dtype not in _DT_SORT_DIM:
+        raise TypeError(f"unsupported key dtype {dtype}")
+    form = 0 if outer == 1 and inner == 1 else 1 if inner == 1 else 2
+    d = {"form": _SORT_DIM_FORMS[form], "outer": outer, "n": n, "inner": inner, "regime": "tile", "tile": 0,
+         "lines_per_tile": 0, "passes": 0, "workgroups": 0, "items": 0, "threads": 0}
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        return d
+    info = _sort_dim_info(outer, n, inner, _DT_SORT_DIM[dtype], dev)
+    d.update(form=_SORT_DIM_FORMS[info[0]], regime=_SORT_DIM_REGIMES[info[1]], tile=info[2], lines_per_tile=info[3],
+             passes=info[4], workgroups=info[5], items=info[6], threads=info[7])
+    return d
+
+
 def sort(keys: torch.Tensor, values: torch.Tensor | None = None, algo: str = "radix", num_bits: int = 8,
-         key_bits: int | None = None, descending: bool = False):
+         key_bits: int | None = None, descending: bool = False, dim: int | None = None):
     """Sort a 1-D tensor of int32 / uint32 / float32 or int64 / uint64 /
     float64 keys, optionally carrying one value per key: 4-byte values with
     32-bit keys, 4- or 8-byte values of any dtype (moved as raw bits) with
@@ -323,7 +454,23 @@ def sort(keys: torch.Tensor, values: torch.Tensor | None = None, algo: str = "ra
     32-bit keys. ``key_bits`` (None = the key width) below the key width
     (radix, non-negative integer keys below ``2**key_bits``) runs only the
     passes covering those bits -- a counting sort when ``key_bits <= 8``.
-    Returns sorted keys (and values)."""
+    Returns sorted keys (and values).
+
+    With ``dim`` (one int, negative allowed): the sort of a tensor of any rank
+    >= 1 along that dimension, as the named pair ``(values, indices)`` of
+    ``torch.sort(keys, dim, descending, stable=True)``. Every line is sorted
+    by the order above, stably in both directions; ``values`` (contiguous,
+    ``keys``' shape and dtype) is ``keys`` gathered at ``indices`` (int64
+    positions along ``dim``) bit for bit, NaN payloads and zero signs
+    included. ``indices`` replaces carried values: ``values``, ``algo``,
+    ``num_bits`` and ``key_bits`` must stay at their defaults (``TypeError``).
+    GPU: lines that fit the tile of ``csrc/hip/sort_dim.hip`` are sorted in
+    LDS, several short lines per workgroup (:func:`sort_dim_launch_info`);
+    longer lines are composed from two 1-D key-value sorts and take fewer
+    than 2**32 elements. CPU: ``cme_cpu_sort_dim``. No host synchronisation."""
+    if dim is not None:
+        _check_dim_args(values, algo, num_bits, key_bits)
+        return SortWithIndices(*_sort_dim(keys, dim, descending))
     if keys.dim() != 1:
         raise ValueError("1-D keys expected")
     n = keys.numel()
@@ -392,12 +539,16 @@ def sort(keys: torch.Tensor, values: torch.Tensor | None = None, algo: str = "ra
     return _from_u32(k, dtype)
 
 
-def argsort(keys: torch.Tensor, descending: bool = False) -> torch.Tensor:
+def argsort(keys: torch.Tensor, descending: bool = False, dim: int | None = None) -> torch.Tensor:
     """The stable sorting permutation of 1-D ``keys`` (any dtype :func:`sort`
     takes, GPU or CPU) as int64: ``keys[argsort(keys)]`` is ``sort(keys)``,
     and equal keys keep their input order, as ``torch.sort(keys, stable=True,
     descending=...).indices``. A key-value radix sort carrying 32-bit
-    positions (the sort's limit is n < 2**32), widened once at the end."""
+    positions (the sort's limit is n < 2**32), widened once at the end.
+    With ``dim``: the ``indices`` of ``sort(keys, dim=dim, descending=...)``,
+    for a tensor of any rank >= 1."""
+    if dim is not None:
+        return _sort_dim(keys, dim, descending)[1]
     if keys.dim() != 1:
         raise ValueError("1-D keys expected")
     n = keys.numel()

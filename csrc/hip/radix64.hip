@@ -44,22 +44,7 @@ constexpr int k64Waves = k64Threads / kWave;
 constexpr int k64Items = 8;
 constexpr int k64Tile = k64Threads * k64Items;  // 8192 keys
 constexpr int kUp64Threads = 256;
-constexpr uint64_t kSign64 = 0x8000000000000000ull;
-
-// mode: bits 0-1 key kind (0 uint64, 1 int64, 2 float64), bit 2 descending
-__device__ __forceinline__ uint64_t rx64_key_in(uint64_t k, int mode) {
-    const int kind = mode & 3;
-    if (kind == 1) k ^= kSign64;
-    if (kind == 2) k ^= (uint64_t)((long long)k >> 63) | kSign64;
-    return (mode & 4) ? ~k : k;
-}
-__device__ __forceinline__ uint64_t rx64_key_out(uint64_t u, int mode) {
-    const int kind = mode & 3;
-    if (mode & 4) u = ~u;
-    if (kind == 1) u ^= kSign64;
-    if (kind == 2) u ^= ~(uint64_t)((long long)u >> 63) | kSign64;
-    return u;
-}
+// (rx64_key_in / rx64_key_out: sort_kernels.h, shared with sort_dim.hip)
 __device__ __forceinline__ uint32_t digit64(uint64_t k, int shift) { return (uint32_t)(k >> shift) & (kBins - 1); }
 
 // Keys are 8-byte aligned; a view (keys[1:]) need not be 16-byte aligned.

@@ -35,6 +35,23 @@ __device__ __forceinline__ uint32_t rx_key_out(uint32_t u, int mode) {
     return u;
 }
 
+// 64-bit keys (radix64.hip, sort_dim.hip). mode: bits 0-1 key kind (0 uint64,
+// 1 int64, 2 float64), bit 2 descending (the complemented code)
+constexpr uint64_t kSign64 = 0x8000000000000000ull;
+__device__ __forceinline__ uint64_t rx64_key_in(uint64_t k, int mode) {
+    const int kind = mode & 3;
+    if (kind == 1) k ^= kSign64;
+    if (kind == 2) k ^= (uint64_t)((long long)k >> 63) | kSign64;
+    return (mode & 4) ? ~k : k;
+}
+__device__ __forceinline__ uint64_t rx64_key_out(uint64_t u, int mode) {
+    const int kind = mode & 3;
+    if (mode & 4) u = ~u;
+    if (kind == 1) u ^= kSign64;
+    if (kind == 2) u ^= ~(uint64_t)((long long)u >> 63) | kSign64;
+    return u;
+}
+
 template <int UNR, bool kUpVecCheck = true>
 __global__ __launch_bounds__(kSortThreads) void radix_upsweep_kernel(const uint32_t* __restrict__ keys, long long n,
                                                                      long long chunk, int shift, int nblocks,

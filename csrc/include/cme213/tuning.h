@@ -48,6 +48,8 @@ enum TuneKey : int {
     kTuneMergeBlockSort,   // CME_MERGE_BLOCK_SORT: keys-only 16384-key block sort, 1 LDS radix (4 digit passes), 0 merge network
     kTuneScanDimChunks,    // CME_SCAN_DIM_CHUNKS: chunks along the scanned dimension of scan(dim=) (0 = rule)
     kTuneScanDimMaxBlocks, // CME_SCAN_DIM_MAXBLOCKS: grid cap of the scan(dim=) kernels (0 = rule)
+    kTuneSortDimMaxN,      // CME_SORT_DIM_MAX_N: longest line the tile kernel of sort(dim=) takes (0 = rule = its tile)
+    kTuneSortDimLanes,     // CME_SORT_DIM_LANES: sort(dim=) tile ranks, 1 lane order where the probe passed, 0 ballot match
     kTuneCount
 };
 
