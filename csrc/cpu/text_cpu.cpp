@@ -47,7 +47,7 @@ void privatised_hist(long long n, int nbins, int32_t* out, Fn&& body) {
 }  // namespace
 
 CME_CPU_EXPORT int cme_cpu_histogram_u8(const uint8_t* x, long long n, int lo, int nbins, int32_t* out) {
-    if (nbins <= 0) return 1;
+    if (nbins <= 0 || nbins > 256) return 1;
     privatised_hist(n, nbins, out, [&](long long b, long long e, int64_t* h) {
         for (long long i = b; i < e; ++i) {
             const int v = (int)x[i] - lo;
@@ -84,6 +84,7 @@ CME_CPU_EXPORT int cme_cpu_residue_hist(const uint8_t* t, long long n, int perio
 
 // counts[k] = #{i : t[i] == t[i + s0 + k]}, k in [0, ns)
 CME_CPU_EXPORT int cme_cpu_match_count(const uint8_t* t, long long n, int s0, int ns, int64_t* out) {
+    if (s0 < 0 || ns < 0) return 1;
     for (int k = 0; k < ns; ++k) {
         const long long s = (long long)s0 + k;
         int64_t c = 0;

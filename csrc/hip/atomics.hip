@@ -102,8 +102,10 @@ CME_EXPORT int cme_monte_carlo_pi(long long samples, unsigned long long seed, un
 
 // out: one int (order-mapped float); decode on the host.
 CME_EXPORT int cme_global_max(const float* in, long long n, int* out, void* stream) {
+    if (n <= 0) return (int)hipErrorInvalidValue;  // the maximum of nothing
     hipStream_t s = as_stream(stream);
-    CME_TRY(hipMemsetAsync(out, 0x80, 4, s));  // 0x80808080: far below any mapped float
+    // INT_MIN: below the image of every float (f2ord(-inf) = 0x807fffff is the lowest)
+    CME_TRY(hipMemsetD32Async((hipDeviceptr_t)out, INT32_MIN, 1, s));
     hipLaunchKernelGGL(global_max_kernel, dim3(stream_grid((n + 15) / 16, 256, 4)), dim3(256), 0, s, in, n, out);
     CME_LAUNCH_STATUS();
 }

@@ -142,7 +142,10 @@ CME_EXPORT int cme_shift_cipher(const uint8_t* in, uint8_t* out, long long n, in
     hipStream_t s = as_stream(stream);
     const uint8_t sh = (uint8_t)shift;
     const uint32_t s4 = 0x01010101u * sh;
-    if (block <= 0) block = 256;
+    if (block == 0) block = 256;
+    if (block < 0 || block > 256) return (int)hipErrorInvalidValue;  // the kernels' __launch_bounds__
+    if (n <= 0) return n < 0 ? (int)hipErrorInvalidValue : 0;
+    if (width != 1 && (((uintptr_t)in | (uintptr_t)out) % width)) width = 1;
     size_t body = 0;
     if (width == 1) {
         hipLaunchKernelGGL(shift_u8_kernel, dim3(stream_grid(n, block)), dim3(block), 0, s, in, out, (size_t)n, sh);
@@ -173,23 +176,29 @@ CME_EXPORT int cme_shift_cipher(const uint8_t* in, uint8_t* out, long long n, in
 
 CME_EXPORT int cme_copy_bytes(const void* in, void* out, long long nbytes, void* stream) {
     hipStream_t s = as_stream(stream);
-    size_t m = (size_t)nbytes / 16;
+    // 16-B lanes need both ends aligned to 16 B; any other pair goes by bytes
+    const bool aligned = (((uintptr_t)in | (uintptr_t)out) % 16) == 0;
+    size_t m = aligned ? (size_t)nbytes / 16 : 0;
     // measured best on MI355X (benchmarks/tune_copy.py, profiles/copy_tune_r2.log):
     // one-shot 4 KB tiles, one 16-B non-temporal vector per lane: 6.54 TB/s
     // on 1 GiB (round 1's grid-stride persistent copy: 5.96)
     if (m) hipLaunchKernelGGL(copy_flat_kernel<1>, dim3(cdiv(m, 256)), dim3(256), 0, s, (const u32x4*)in,
                               (u32x4*)out, m);
     size_t body = m * 16;
-    if ((size_t)nbytes > body)
-        hipLaunchKernelGGL(shift_u8_kernel, dim3(1), dim3(64), 0, s, (const uint8_t*)in + body, (uint8_t*)out + body,
-                           (size_t)nbytes - body, (uint8_t)0);
+    if ((size_t)nbytes > body) {
+        const size_t rem = (size_t)nbytes - body;
+        hipLaunchKernelGGL(shift_u8_kernel, dim3(stream_grid(rem, 256)), dim3(256), 0, s, (const uint8_t*)in + body,
+                           (uint8_t*)out + body, rem, (uint8_t)0);
+    }
     CME_LAUNCH_STATUS();
 }
 
 CME_EXPORT int cme_mul_f32(float* a, const float* b, long long n, void* stream) {
-    size_t n4 = (size_t)n / 4;
-    hipLaunchKernelGGL(mul_f32_kernel, dim3(stream_grid(n4 ? n4 : 1, 256)), dim3(256), 0, as_stream(stream), a, b,
-                       n4, (size_t)n);
+    if (n <= 0) return n < 0 ? (int)hipErrorInvalidValue : 0;
+    // float4 lanes need both operands aligned to 16 B; otherwise the scalar loop takes everything
+    size_t n4 = (((uintptr_t)a | (uintptr_t)b) % 16) ? 0 : (size_t)n / 4;
+    hipLaunchKernelGGL(mul_f32_kernel, dim3(stream_grid(n4 ? n4 : (size_t)n, 256)), dim3(256), 0, as_stream(stream),
+                       a, b, n4, (size_t)n);
     CME_LAUNCH_STATUS();
 }
 

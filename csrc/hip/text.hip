@@ -29,6 +29,15 @@ __global__ __launch_bounds__(256) void histogram_u8_kernel(const uint8_t* __rest
     for (int i = threadIdx.x; i < 4 * nbins; i += 256) sh[i] = 0;
     __syncthreads();
     int* h = sh + wid * nbins;
+    // 4-byte loads need a 4-byte aligned address: block 0 counts the bytes
+    // before the first aligned one, every block then starts from there
+    const long long head = min((long long)((4 - (uintptr_t)in % 4) % 4), n);
+    if (blockIdx.x == 0 && threadIdx.x < head) {
+        const int b = (int)in[threadIdx.x] - lo;
+        if (b >= 0 && b < nbins) atomicAdd(&h[b], 1);
+    }
+    in += head;
+    n -= head;
     const long long stride = (long long)gridDim.x * 256 * 4;
     for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += stride) {
         uint32_t w;
@@ -98,14 +107,14 @@ __global__ __launch_bounds__(256) void match_count_kernel(const uint8_t* __restr
     const long long t0 = (long long)blockIdx.x * kMcTile;
     for (int i = threadIdx.x; i < kMcTile; i += 256) A[i] = t0 + i < n ? t[t0 + i] : 0;
     for (int i = threadIdx.x; i < kMcTile + ns; i += 256) {
-        const long long g = t0 + s0 + i;
+        const long long g = t0 + (long long)s0 + i;
         Bh[i] = g < n ? t[g] : 0;
     }
     __syncthreads();
     const int lane = lane_id();
-    for (int s = s0 + threadIdx.x / kWave; s < s0 + ns; s += 4) {
+    for (int d = threadIdx.x / kWave; d < ns; d += 4) {
         unsigned c = 0;
-        const int d = s - s0;
+        const long long s = (long long)s0 + d;
         for (int j = lane; j < kMcTile; j += kWave)
             if (t0 + j + s < n) c += A[j] == Bh[j + d];
         const unsigned tot = wave_reduce(c);
@@ -169,10 +178,11 @@ __global__ __launch_bounds__(256) void vigenere_kernel(const uint8_t* __restrict
                                                        const int* __restrict__ shifts, int period, int sign,
                                                        uint8_t* __restrict__ out) {
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        int c = (int)in[i] + sign * shifts[i % period];
-        while (c > 'z') c -= 26;
-        while (c < 'a') c += 26;
-        out[i] = (uint8_t)c;
+        // the CPU backend's arithmetic: the shift is reduced first, so any
+        // int32 shift (INT_MIN too) costs the same and nothing overflows
+        int v = ((int)in[i] - 'a' + sign * (shifts[i % period] % 26)) % 26;
+        if (v < 0) v += 26;
+        out[i] = (uint8_t)('a' + v);
     }
 }
 
@@ -196,6 +206,7 @@ CME_EXPORT int cme_digraphs(const uint8_t* in, long long n, int* out, void* stre
 }
 
 CME_EXPORT int cme_residue_hist(const uint8_t* in, long long n, int period, int* out, void* stream) {
+    if (period <= 0 || period > INT32_MAX / 26) return (int)hipErrorInvalidValue;
     hipStream_t s = as_stream(stream);
     const size_t nb = (size_t)period * 26;
     CME_TRY(hipMemsetAsync(out, 0, nb * sizeof(int), s));
@@ -205,11 +216,15 @@ CME_EXPORT int cme_residue_hist(const uint8_t* in, long long n, int period, int*
     CME_LAUNCH_STATUS();
 }
 
-// counts: uint64 [ns], shifts s0 .. s0+ns-1 (s0 >= 1), batches of 1024.
+// counts: uint64 [ns], shifts s0 .. s0+ns-1 (s0 >= 0, s0 + ns within int),
+// batches of 1024. An empty text leaves every count at 0.
 CME_EXPORT int cme_match_count(const uint8_t* t, long long n, int s0, int ns, unsigned long long* counts,
                                void* stream) {
+    if (n < 0 || s0 < 0 || ns < 0 || (long long)s0 + ns > INT32_MAX) return (int)hipErrorInvalidValue;
+    if (ns == 0) return 0;
     hipStream_t s = as_stream(stream);
     CME_TRY(hipMemsetAsync(counts, 0, ns * sizeof(unsigned long long), s));
+    if (n == 0) return 0;
     for (int b = 0; b < ns; b += 1024) {
         const int cnt = ns - b < 1024 ? ns - b : 1024;
         hipLaunchKernelGGL(match_count_kernel, dim3(cdiv(n, kMcTile)), dim3(256), 0, s, t, n, s0 + b, cnt,
@@ -222,6 +237,7 @@ CME_EXPORT int cme_match_count(const uint8_t* t, long long n, int s0, int ns, un
 // receives the number of letters kept.
 CME_EXPORT int cme_sanitize(const uint8_t* in, long long n, uint8_t* out, int* part, int* count_out, void* stream) {
     hipStream_t s = as_stream(stream);
+    if (n <= 0) return (int)hipMemsetAsync(count_out, 0, sizeof(int), s);  // nothing kept, no chunk to size
     const int blocks = n < 1024 * 4096LL ? (int)cdiv(n, 4096) : 1024;
     const long long chunk = (n + blocks - 1) / blocks;
     hipLaunchKernelGGL(sanitize_count_kernel, dim3(blocks), dim3(256), 0, s, in, n, chunk, part);
@@ -232,6 +248,8 @@ CME_EXPORT int cme_sanitize(const uint8_t* in, long long n, uint8_t* out, int* p
 
 CME_EXPORT int cme_vigenere(const uint8_t* in, long long n, const int* shifts, int period, int sign, uint8_t* out,
                             void* stream) {
+    if (period <= 0) return (int)hipErrorInvalidValue;
+    if (n <= 0) return 0;
     hipLaunchKernelGGL(vigenere_kernel, dim3(stream_grid(n, 256)), dim3(256), 0, as_stream(stream), in, n, shifts,
                        period, sign, out);
     CME_LAUNCH_STATUS();
