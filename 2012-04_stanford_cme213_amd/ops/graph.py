@@ -1,7 +1,8 @@
 """CSR graph propagation (PageRank, hw1 p2).
 
 ``propagate(g, x)`` is one sweep ``out[i] = 0.5/N + 0.5*sum_j x[e_j]*inv[e_j]``
-(``hw/hw1/programming/pagerank.cu:70-83``); ``iterate`` runs the 20-sweep
+(``hw/hw1/programming/pagerank.cu:70-83``) and also returns the prescaled
+vector ``out*inv`` the next sweep gathers from; ``iterate`` runs the 20-sweep
 ping-pong of ``device_graph_iterate`` (``:86-143``) with the prescaled-gather
 kernels and no host synchronisation between sweeps.
 """
@@ -67,6 +68,30 @@ class BlockedGraph:
         return self.inv_deg.numel()
 
 
+GROUPS = (1, 2, 4, 8, 16)  # lanes per row of cme_pr_propagate
+BLOCKED_GROUPS = (1, 2, 4, 8)  # ... of cme_pr_propagate_blocked
+
+
+def _check_group(g, group: int) -> None:
+    ok = BLOCKED_GROUPS if isinstance(g, BlockedGraph) else GROUPS
+    if group not in ok:
+        kind = "a column-blocked graph" if isinstance(g, BlockedGraph) else "a CSR graph"
+        raise ValueError(f"group must be one of {ok} for {kind}, got {group!r}")
+
+
+def _check_vector(g, x: torch.Tensor, what: str) -> None:
+    """``x`` is a contiguous float32 vector of g.n entries on g's device (the
+    kernels index it with the graph's node numbers and nothing else checks)."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise TypeError(f"{what} must be a float32 tensor")
+    if x.dim() != 1 or x.numel() != g.n:
+        raise ValueError(f"{what} must have shape ({g.n},), got {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    if x.device != g.inv_deg.device:
+        raise ValueError(f"{what} is on {x.device}, the graph on {g.inv_deg.device}")
+
+
 def _edge_order(key: torch.Tensor) -> torch.Tensor:
     """Stable sorting permutation of the int64 (block, row) keys: the edges of
     one (block, row) keep their CSR order. Still ``torch.sort``:
@@ -93,8 +118,12 @@ def block_columns(g: CSRGraph, blocks: int = 4) -> BlockedGraph:
     """Column-blocked copy of ``g`` (one-time preprocessing with tensor ops,
     on g's device): a sweep then gathers from one 1/blocks slice of the vector
     at a time (:func:`iterate` with ``blocks``)."""
+    if isinstance(blocks, bool) or not isinstance(blocks, int) or blocks < 1:
+        raise ValueError(f"blocks must be a positive integer, got {blocks!r}")
     n = g.n
     dev = g.edges.device
+    if n == 0:
+        return BlockedGraph(torch.zeros(1, dtype=torch.int32, device=dev), g.edges, g.inv_deg, blocks)
     deg = (g.indices[1:] - g.indices[:-1]).to(torch.int64)
     row = torch.repeat_interleave(torch.arange(n, device=dev), deg)
     bs = (n + blocks - 1) // blocks
@@ -110,7 +139,11 @@ def block_columns(g: CSRGraph, blocks: int = 4) -> BlockedGraph:
 
 def propagate_ref(g: CSRGraph, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """One sweep with the reference's two-gathers-per-edge arithmetic."""
-    out = torch.empty_like(x) if out is None else out
+    _check_vector(g, x, "x")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _check_vector(g, out, "out")
     if x.is_cuda:
         _ext.call_hip("cme_pr_propagate_ref", g.indices.data_ptr(), g.edges.data_ptr(), x.data_ptr(),
                       out.data_ptr(), g.inv_deg.data_ptr(), g.n, _ext.stream_ptr(x.device))
@@ -120,15 +153,62 @@ def propagate_ref(g: CSRGraph, x: torch.Tensor, out: torch.Tensor | None = None)
     return out
 
 
+def propagate(g, x: torch.Tensor, group: int = 1, blocks: int | None = None):
+    """One sweep from an unscaled ``x``: returns ``(out, y_next)`` with
+    ``y_next = out * inv_deg``, the prescaled vector the next sweep gathers.
+    GPU: one prescale launch and one sweep of the prescaled-gather kernels
+    (``group`` lanes per row); with a :class:`BlockedGraph`, or ``blocks``
+    given (``block_columns(g, blocks)`` first), the column-blocked sweep.
+    CPU: the reference arithmetic (``group`` only validated)."""
+    if blocks is not None:
+        if isinstance(g, BlockedGraph):
+            if blocks != g.blocks:
+                raise ValueError(f"blocks = {blocks!r}, but the graph has {g.blocks} column blocks")
+        else:
+            g = block_columns(g, blocks)
+    _check_group(g, group)
+    _check_vector(g, x, "x")
+    blocked = isinstance(g, BlockedGraph)
+    if not x.is_cuda:
+        if blocked:
+            raise ValueError("column-blocked sweeps run on the GPU")
+        out = propagate_ref(g, x)
+        return out, out * g.inv_deg
+    s = _ext.stream_ptr(x.device)
+    n = g.n
+    y, out, y_next = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    _ext.call_hip("cme_pr_prescale", x.data_ptr(), g.inv_deg.data_ptr(), y.data_ptr(), n, s)
+    if blocked:
+        acc = torch.empty_like(x)
+        _ext.call_hip("cme_pr_propagate_blocked", g.rp.data_ptr(), g.edges.data_ptr(), y.data_ptr(), acc.data_ptr(),
+                      out.data_ptr(), y_next.data_ptr(), g.inv_deg.data_ptr(), n, g.blocks, group, s)
+    else:
+        _ext.call_hip("cme_pr_propagate", g.indices.data_ptr(), g.edges.data_ptr(), y.data_ptr(), out.data_ptr(),
+                      y_next.data_ptr(), g.inv_deg.data_ptr(), n, group, s)
+    return out, y_next
+
+
+def _check_iters(iters: int) -> None:
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
+        raise ValueError(f"iters must be a non-negative integer, got {iters!r}")
+    if iters % 2:
+        raise ValueError("iters must be even (A/B ping-pong, as in the reference)")
+
+
 def iterate(g, x0: torch.Tensor, iters: int = 20, group: int = 1) -> torch.Tensor:
     """``iters`` sweeps (even, like the reference); returns the final vector.
     group = lanes per row on the GPU (1 keeps the CPU summation order).
     ``g`` may be a :class:`BlockedGraph` (GPU): column-blocked sweeps, each
-    row summed block by block (same terms, different association order)."""
+    row summed block by block (same terms, different association order).
+    ``iters == 0`` returns a copy of ``x0``; ``x0`` is a contiguous float32
+    vector of ``g.n`` entries on the graph's device."""
+    _check_iters(iters)
+    _check_group(g, group)
+    _check_vector(g, x0, "x0")
     if isinstance(g, BlockedGraph):
         return _iterate_blocked(g, x0, iters, group)
-    if iters % 2:
-        raise ValueError("iters must be even (A/B ping-pong, as in the reference)")
+    if iters == 0:
+        return x0.clone()
     if not x0.is_cuda:
         a, b = x0.clone(), torch.empty_like(x0)
         for _ in range(iters // 2):
@@ -148,10 +228,10 @@ def iterate(g, x0: torch.Tensor, iters: int = 20, group: int = 1) -> torch.Tenso
 
 
 def _iterate_blocked(g: BlockedGraph, x0: torch.Tensor, iters: int, group: int) -> torch.Tensor:
-    if iters % 2:
-        raise ValueError("iters must be even (A/B ping-pong, as in the reference)")
     if not x0.is_cuda:
         raise ValueError("column-blocked sweeps run on the GPU")
+    if iters == 0:
+        return x0.clone()
     s = _ext.stream_ptr(x0.device)
     n = g.n
     out = torch.empty_like(x0)

@@ -142,6 +142,8 @@ CME_EXPORT int cme_pr_propagate_blocked(const uint32_t* rp, const uint32_t* edge
                                         void* stream) {
     hipStream_t s = as_stream(stream);
     if (blocks < 1) return (int)hipErrorInvalidValue;
+    if (group != 1 && group != 2 && group != 4 && group != 8) return (int)hipErrorInvalidValue;
+    if (n <= 0) return 0;  // no rows: a zero-block grid is an invalid launch, not a no-op
     for (int b = 0; b < blocks; ++b) {
         const uint32_t* r = rp + (size_t)b * n;
         const int first = b == 0, last = b == blocks - 1;
@@ -170,12 +172,14 @@ CME_EXPORT int cme_pr_propagate_blocked(const uint32_t* rp, const uint32_t* edge
 }
 
 CME_EXPORT int cme_pr_prescale(const float* x, const float* inv, float* y, int n, void* stream) {
+    if (n <= 0) return 0;
     hipLaunchKernelGGL(prescale_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), x, inv, y, n);
     CME_LAUNCH_STATUS();
 }
 
 CME_EXPORT int cme_pr_propagate_ref(const uint32_t* idx, const uint32_t* edges, const float* in, float* out,
                                     const float* inv, int n, void* stream) {
+    if (n <= 0) return 0;
     hipLaunchKernelGGL(pr_ref_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), idx, edges, in, out, inv, n);
     CME_LAUNCH_STATUS();
 }
@@ -184,6 +188,8 @@ CME_EXPORT int cme_pr_propagate_ref(const uint32_t* idx, const uint32_t* edges, 
 CME_EXPORT int cme_pr_propagate(const uint32_t* idx, const uint32_t* edges, const float* y_in, float* out,
                                 float* y_out, const float* inv, int n, int group, void* stream) {
     hipStream_t s = as_stream(stream);
+    if (group != 1 && group != 2 && group != 4 && group != 8 && group != 16) return (int)hipErrorInvalidValue;
+    if (n <= 0) return 0;
     switch (group) {
         case 1:
             hipLaunchKernelGGL(pr_scalar_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, idx, edges, y_in, out, y_out,

@@ -271,7 +271,8 @@ int launch_vec_tile(const float* in, float* out, int rows, int cols, hipStream_t
 CME_EXPORT int cme_transpose_tune(const float* in, float* out, int rows, int cols, int tr, int tc, int remap,
                                   void* stream) {
     hipStream_t s = as_stream(stream);
-    if ((rows % 4) || (cols % 4)) return (int)hipErrorInvalidValue;
+    if (rows < 0 || cols < 0 || (rows % 4) || (cols % 4)) return (int)hipErrorInvalidValue;
+    if (rows == 0 || cols == 0) return 0;
 #define CME_VT(TR, TC)                                                                      \
     if (tr == TR && tc == TC) {                                                             \
         switch (remap) {                                                                    \
@@ -301,6 +302,8 @@ CME_EXPORT int cme_transpose_tune(const float* in, float* out, int rows, int col
 
 CME_EXPORT int cme_transpose_f32(const float* in, float* out, int rows, int cols, int variant, void* stream) {
     hipStream_t s = as_stream(stream);
+    if (rows < 0 || cols < 0 || variant < 0 || variant > 11) return (int)hipErrorInvalidValue;
+    if (rows == 0 || cols == 0) return 0;  // nothing to move: a zero-block grid is an invalid launch, not a no-op
     dim3 grid(cdiv(cols, kT), cdiv(rows, kT));
     switch (variant) {
         case 0: hipLaunchKernelGGL(copy_kernel, grid, dim3(256), 0, s, in, out, rows, cols); break;
@@ -334,7 +337,9 @@ CME_EXPORT int cme_transpose_f32(const float* in, float* out, int rows, int cols
             break;
         case 10:
         case 11:
-            if (rows != cols) return (int)hipErrorInvalidValue;  // diagnostics: square only
+            // diagnostics: square, whole tiles only (in a partial tile the
+            // coarse kernel would copy LDS cells that no thread wrote)
+            if (rows != cols || rows % kT) return (int)hipErrorInvalidValue;
             if (variant == 10)
                 hipLaunchKernelGGL((grain_kernel<0>), grid, dim3(256), 0, s, in, out, rows, cols);
             else
@@ -346,6 +351,8 @@ CME_EXPORT int cme_transpose_f32(const float* in, float* out, int rows, int cols
 }
 
 CME_EXPORT int cme_transpose_reps_f32(const float* in, float* out, int rows, int cols, int reps, void* stream) {
+    if (rows < 0 || cols < 0 || reps < 1) return (int)hipErrorInvalidValue;  // reps < 1 would leave out unwritten
+    if (rows == 0 || cols == 0) return 0;
     dim3 grid(cdiv(cols, kT), cdiv(rows, kT));
     hipLaunchKernelGGL(tile_reps_kernel, grid, dim3(256), 0, as_stream(stream), in, out, rows, cols, reps);
     CME_LAUNCH_STATUS();
