@@ -11,6 +11,7 @@ index of set flags                :func:`nonzero`
 ``lower_bound``/``upper_bound``   :func:`lower_bound`, :func:`upper_bound`
 ``reduce_by_key`` (sorted keys)   :func:`reduce_by_key`
 dense / sparse histogram          :func:`histogram_dense`, :func:`histogram_sparse`
+histogram by atomics (Lecture21)  :func:`bincount` (unsorted uint8 / int32 / int64)
 counting sort (Lecture16)         :func:`counting_sort`
 ``max_element``/``min_element``   :func:`max_element`, :func:`min_element`
 ``inner_product``                 :func:`inner_product` (``op="mul"|"eq"``)
@@ -48,6 +49,10 @@ _ext.proto(_ext.CPU_PROTOS, "cme_cpu_search", "pqpqiip")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_seg_reduce", "ppqiip")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_arg_reduce", "pqiipp")
 _ext.proto(_ext.CPU_PROTOS, "cme_cpu_inner_product", "ppqip")
+_ext.proto(_ext.HIP_PROTOS, "cme_bincount", "pqiqpp")
+_ext.proto(_ext.HIP_PROTOS, "cme_bincount_plan", "qiqp")
+_ext.proto(_ext.CPU_PROTOS, "cme_cpu_bincount", "pqiqp")
+_ext.proto(_ext.CPU_PROTOS, "cme_cpu_bincount_path", "pqiqpi")
 
 _SEARCH_DT = {torch.float32: 0, torch.int32: 1, torch.uint32: 2, torch.int64: 3, torch.float64: 4}
 _RED_DT = {torch.float32: 0, torch.int32: 1, torch.int64: 3, torch.float64: 4}
@@ -255,6 +260,154 @@ def histogram_sparse(sorted_: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]
     constant-1 value stream (``solve_cipher_solution.cu:185-200``)."""
     ones = torch.ones(sorted_.numel(), dtype=torch.int32, device=sorted_.device)
     return reduce_by_key(sorted_, ones, "sum")
+
+
+_BINCOUNT_DT = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}  # dtype -> the native element size
+_BINCOUNT_REGIMES = {1: "lds", 2: "window", 3: "global", 4: "sorted"}
+# CPU backend: 0 the rule, 1 serial, 2 per-thread tables, 3 bins partitioned over the threads (tests force each)
+BINCOUNT_CPU_PATH = 0
+
+
+def _bincount_plan(n: int, esize: int, nbins: int) -> list[int]:
+    """cme_bincount_plan under the current knobs; ``ValueError`` where the
+    regime forced by ``bincount_regime`` cannot run the shape."""
+    info = (ctypes.c_longlong * 11)()
+    if _ext._fn("hip", "cme_bincount_plan")(n, esize, nbins, ctypes.addressof(info)) != 0:
+        from ..utils import tuning
+
+        raise ValueError(f"bincount: the forced regime (bincount_regime={tuning.get('bincount_regime')}) cannot run "
+                         f"n={n}, nbins={nbins}, {esize}-byte elements")
+    return [int(v) for v in info]
+
+
+def _bincount_sorted(x: torch.Tensor, nbins: int, out: torch.Tensor) -> torch.Tensor:
+    """The ``sorted`` regime: the dense histogram of the sorted copy. Unlike
+    :func:`histogram_dense`, bin 0 starts at the first element >= 0, so
+    negative elements are not counted."""
+    s = _sort(x)
+    q = torch.arange(nbins, dtype=x.dtype, device=x.device)
+    ub = upper_bound(s, q)
+    first = lower_bound(s, torch.zeros(1, dtype=x.dtype, device=x.device))
+    torch.sub(ub, torch.cat([first, ub[:-1]]), out=out)
+    return out
+
+
+def _bincount_fixed(x: torch.Tensor, nbins: int, out: torch.Tensor | None) -> torch.Tensor:
+    esize = _BINCOUNT_DT[x.dtype]
+    if out is None:
+        out = torch.empty(nbins, dtype=torch.int64, device=x.device)
+    if nbins == 0:
+        return out
+    if not x.is_cuda:
+        if BINCOUNT_CPU_PATH:
+            _ext.call_cpu("cme_cpu_bincount_path", x.data_ptr(), x.numel(), esize, nbins, out.data_ptr(),
+                          BINCOUNT_CPU_PATH)
+        else:
+            _ext.call_cpu("cme_cpu_bincount", x.data_ptr(), x.numel(), esize, nbins, out.data_ptr())
+        return out
+    with torch.cuda.device(x.device):
+        if _bincount_plan(x.numel(), esize, nbins)[0] == 4:
+            return _bincount_sorted(x, nbins, out) if x.numel() else out.zero_()
+        _ext.call_hip("cme_bincount", x.data_ptr(), x.numel(), esize, nbins, out.data_ptr(), _ext.stream_ptr(x.device))
+    return out
+
+
+def bincount(x: torch.Tensor, minlength: int = 0, nbins: int | None = None,
+             out: torch.Tensor | None = None) -> torch.Tensor:
+    """Counts of the values ``0, 1, 2, ...`` in UNSORTED integer data (int64).
+
+    ``x``: a 1-D ``uint8``, ``int32`` or ``int64`` tensor on the CPU or the
+    GPU, any contiguous view at element alignment (``x[1:]`` runs without a
+    padded copy); a non-contiguous view is made contiguous first. Other dtypes
+    raise ``TypeError``, other ranks ``ValueError``.
+
+    ``nbins=None``: ``torch.bincount(x, minlength=minlength)`` exactly -- the
+    result has ``max(max(x) + 1, minlength)`` entries, a negative element
+    raises ``ValueError``, an empty ``x`` gives ``zeros(minlength)``. The
+    length is data dependent, so this form reads the extremes back to the host
+    once (``scan.reduce`` "min" / "max"; uint8 counts into 256 bins and trims).
+
+    ``nbins=K``: exactly ``K`` entries. An element outside ``[0, K)`` is not
+    counted and raises nothing; the comparison is made in the element's own
+    width (an int64 ``2**32 + 3`` is out of range for ``K = 8``). No host
+    synchronisation, no data-dependent shape. ``minlength`` must stay 0.
+    ``out``: a contiguous int64 tensor of ``K`` entries on ``x``'s device,
+    overwritten (not accumulated into) and returned; this form only.
+
+    GPU: ``csrc/hip/bincount.hip`` -- per-workgroup LDS tables (``lds``), the
+    same over bin windows (``window``), one global atomic per element
+    (``global``), or the histogram of the sorted copy (``sorted``);
+    :func:`bincount_launch_info` reports which. Integer counts are exact
+    whatever the order of the atomics, so every run gives the same bits. CPU:
+    ``cme_cpu_bincount`` (OpenMP).
+
+    There is no ``weights=``: float atomics are not reproducible, and the
+    deterministic weighted form exists as ``sort`` + :func:`reduce_by_key`.
+    Float binning (``histc``) and counting along a dimension are out of scope
+    too."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("bincount: x must be a tensor")
+    _dtype_code(_BINCOUNT_DT, x, "bincount")
+    if x.dim() != 1:
+        raise ValueError(f"bincount: x must be 1-D, got {x.dim()} dimensions")
+    if isinstance(minlength, bool) or not isinstance(minlength, int) or minlength < 0:
+        raise ValueError(f"bincount: minlength must be a non-negative integer, got {minlength!r}")
+    x = x.contiguous()
+    if nbins is not None:
+        if isinstance(nbins, bool) or not isinstance(nbins, int) or nbins < 0:
+            raise ValueError(f"bincount: nbins must be a non-negative integer, got {nbins!r}")
+        if minlength != 0:
+            raise ValueError("bincount: minlength goes with nbins=None; with nbins given the length is nbins")
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.int64:
+                raise TypeError("bincount: out must be an int64 tensor")
+            if out.dim() != 1 or out.numel() != nbins:
+                raise ValueError(f"bincount: out must have shape ({nbins},), got {tuple(out.shape)}")
+            if not out.is_contiguous():
+                raise ValueError("bincount: out must be contiguous")
+            if out.device != x.device:
+                raise ValueError(f"bincount: out is on {out.device}, x on {x.device}")
+        return _bincount_fixed(x, nbins, out)
+    if out is not None:
+        raise ValueError("bincount: out= needs nbins (the data-dependent form allocates its result)")
+    if x.numel() == 0:
+        return torch.zeros(minlength, dtype=torch.int64, device=x.device)
+    if x.dtype == torch.uint8:
+        c = _bincount_fixed(x, 256, None)
+        k = max(int(torch.nonzero(c)[-1]) + 1, minlength)  # the one host read
+        return c[:k].clone() if k <= 256 else torch.cat([c, c.new_zeros(k - 256)])
+    from .scan import reduce as _reduce
+
+    lo, hi = torch.stack([_reduce(x, "min"), _reduce(x, "max")]).tolist()  # the one host read
+    if lo < 0:
+        raise ValueError("bincount: x has a negative element (give nbins to leave out-of-range elements uncounted)")
+    return _bincount_fixed(x, max(hi + 1, minlength), None)
+
+
+def bincount_launch_info(n: int, nbins: int, dtype: torch.dtype = torch.int64,
+                         device: torch.device | str = "cuda") -> dict:
+    """How ``bincount(x, nbins=nbins)`` of ``n`` elements runs on ``device``
+    under the current knobs: ``regime`` ("lds", "window", "global", "sorted";
+    "cpu" on the CPU), ``window`` (``W``, the bins of one LDS table),
+    ``windows``, ``copies`` (replicas of a workgroup's table), ``workgroups``
+    (= ``windows * chunks``), ``chunks`` (workgroups per window), ``threads``,
+    ``vector`` (elements of one 16-byte lane vector), ``pass`` (elements one
+    workgroup takes per grid stride), ``lds_bytes`` and ``ws_bytes``. A regime
+    forced where it cannot run raises ``ValueError``. The CPU backend has no
+    plan: it reports ``vector`` and zeros."""
+    if dtype not in _BINCOUNT_DT:
+        names = ", ".join(str(d).split(".")[-1] for d in _BINCOUNT_DT)
+        raise TypeError(f"bincount: unsupported dtype {dtype} (takes {names})")
+    esize = _BINCOUNT_DT[dtype]
+    d = {"regime": "cpu", "window": 0, "windows": 0, "copies": 0, "workgroups": 0, "chunks": 0, "threads": 0,
+         "vector": 16 // esize, "pass": 0, "lds_bytes": 0, "ws_bytes": 0}
+    if torch.device(device).type != "cuda":
+        return d
+    i = _bincount_plan(int(n), esize, int(nbins))
+    d.update(regime=_BINCOUNT_REGIMES[i[0]], window=i[1], windows=i[2], copies=i[3], workgroups=i[4], lds_bytes=i[5],
+             ws_bytes=i[6], threads=i[7], vector=i[8], chunks=i[10])
+    d["pass"] = i[9]
+    return d
 
 
 def counting_sort(keys: torch.Tensor, num_keys: int, values: torch.Tensor | None = None):

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import _ext
+from .algorithms import bincount
 from .scan import scan
 
 _ext.proto(_ext.HIP_PROTOS, "cme_pr_prescale", "pppip")
@@ -114,6 +115,17 @@ def _row_pointers(counts: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     return scan(counts, out=out)
 
 
+def _edge_counts(key: torch.Tensor, nbins: int) -> torch.Tensor:
+    """int64 number of edges per (block, row) key, ``nbins = blocks * n``
+    entries: this library's ``bincount(key, nbins=)``, identical to the
+    ``torch.bincount(key, minlength=nbins)`` it replaced (every key is in
+    range) and not slower over the whole preprocessing (2^21 nodes: 2.598
+    against 2.700 ms, five interleaved runs of each form spreading 0.015-0.020
+    ms; ``benchmarks/bench_bincount.py --block-columns`` swaps this function,
+    profiles/bincount.md)."""
+    return bincount(key, nbins=nbins)
+
+
 def block_columns(g: CSRGraph, blocks: int = 4) -> BlockedGraph:
     """Column-blocked copy of ``g`` (one-time preprocessing with tensor ops,
     on g's device): a sweep then gathers from one 1/blocks slice of the vector
@@ -131,7 +143,7 @@ def block_columns(g: CSRGraph, blocks: int = 4) -> BlockedGraph:
     key = blk * n + row
     order = _edge_order(key)
     edges = g.edges[order].contiguous()
-    counts = torch.bincount(key, minlength=blocks * n)
+    counts = _edge_counts(key, blocks * n)
     rp = torch.zeros(blocks * n + 1, dtype=torch.int64, device=dev)
     _row_pointers(counts, rp[1:])
     return BlockedGraph(rp.to(torch.int32), edges, g.inv_deg, blocks)

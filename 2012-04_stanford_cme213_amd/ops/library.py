@@ -27,6 +27,7 @@ Ops (schema in each docstring; "!" = mutated in place):
 ``transpose``             2-D fp32 transpose
 ``sgemm`` / ``gemv``      C = A B (MFMA), y = A x
 ``copy_if``               stable stream compaction (data-dependent length)
+``bincount_fixed``        int64 counts of the values 0 .. nbins-1 of unsorted integer data
 ========================  ==============================================================
 
 The reference exposes none of this as a library -- every algorithm is a
@@ -307,10 +308,23 @@ def _(x, flags):
     return x.new_empty(n)
 
 
+# ------------------------------------------------------------------ counting
+@torch.library.custom_op(f"{NS}::bincount_fixed", mutates_args=())
+def bincount_fixed(x: Tensor, nbins: int) -> Tensor:
+    """bincount_fixed(Tensor x, int nbins) -> Tensor
+    (int64 counts of the values 0 .. nbins-1 of a 1-D uint8 / int32 / int64 tensor; elements outside are not counted)"""
+    return _alg.bincount(x, nbins=nbins)
+
+
+@bincount_fixed.register_fake
+def _(x, nbins):
+    return x.new_empty(nbins, dtype=torch.int64)
+
+
 OPS = {
     "heat_step": heat_step, "heat_stepn": heat_stepn, "scan": scan, "scan_op": scan_op,
     "scan_dim": scan_dim, "cummax": cummax, "cummin": cummin, "reduce_dim": reduce_dim, "max_dim": max_dim,
     "min_dim": min_dim, "segmented_scan": segmented_scan,
     "sort": sort, "sort_by_key": sort_by_key, "argsort": argsort, "sort_dim": sort_dim, "spmv_csr": spmv_csr, "transpose": transpose, "sgemm": sgemm,
-    "gemv": gemv, "copy_if": copy_if,
+    "gemv": gemv, "copy_if": copy_if, "bincount_fixed": bincount_fixed,
 }

@@ -101,6 +101,7 @@ const TuneEntry kTuneTable[cme::kTuneCount] = {
     {"CME_MERGE_BLOCK_SORT", 1},
     {"CME_SCAN_DIM_CHUNKS", 0},  {"CME_SCAN_DIM_MAXBLOCKS", 0},
     {"CME_SORT_DIM_MAX_N", 0},   {"CME_SORT_DIM_LANES", 1},
+    {"CME_BINCOUNT_REGIME", 0},  {"CME_BINCOUNT_WINDOW", 0},    {"CME_BINCOUNT_MAXBLOCKS", 0},
 };
 std::atomic<long> g_tune_val[cme::kTuneCount];
 std::atomic<int> g_tune_state[cme::kTuneCount];  // 0 not loaded, 1 from env / default, 2 set

@@ -50,6 +50,9 @@ enum TuneKey : int {
     kTuneScanDimMaxBlocks, // CME_SCAN_DIM_MAXBLOCKS: grid cap of the scan(dim=) kernels (0 = rule)
     kTuneSortDimMaxN,      // CME_SORT_DIM_MAX_N: longest line the tile kernel of sort(dim=) takes (0 = rule = its tile)
     kTuneSortDimLanes,     // CME_SORT_DIM_LANES: sort(dim=) tile ranks, 1 lane order where the probe passed, 0 ballot match
+    kTuneBincountRegime,   // CME_BINCOUNT_REGIME: bincount regime, 0 rule, 1 lds, 2 window, 3 global, 4 sorted (forced; an error where it cannot run)
+    kTuneBincountWindow,   // CME_BINCOUNT_WINDOW: bins of one LDS table / window of bincount (0 = rule = 16384)
+    kTuneBincountMaxBlocks, // CME_BINCOUNT_MAXBLOCKS: cap of bincount's input chunks, the workgroups per window (0 = rule)
     kTuneCount
 };
 
